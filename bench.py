@@ -64,6 +64,17 @@ xor_parity as the P-role fold (the cpu_baseline leg's library, kind
 one store in one process; config5_partial -- the e2e block's partial round.
 The output is verified after timing: cleared, one more step, then fold
 conservation plus sampled stripes compared byte for byte with numpy.
+
+A plain run (`bench.py --gpus N --steps K --warmup W`) is the device timing
+alone: set-up, warm-up, the K timed steps, the line (value, ms_per_step, the
+HIP-event roofline figures, the committed profile set).  Everything else
+above -- the verification step, rank 0 under rocprofv3 and the PMC passes, the
+cpu_baseline, e2e and configs legs -- runs with `--full` only (each leg then
+unless its --no-... option is given); without it their blocks are null, as is
+verified_on_device.  `--dump-outputs DIR` (with or without --full) writes what
+the last timed step left in the output buffer, before anything else touches
+it: dump_outputs() names the files.  The inputs are seeded, so two builds run
+with the same arguments can be compared file for file.
 """
 from __future__ import annotations
 
@@ -135,7 +146,22 @@ def parse():
     ap.add_argument("--allow-shared", action="store_true",
                     help="run N ranks even when fewer than N distinct GPUs exist (rehearsal; "
                          "the line then says shared_gpu true and counts distinct GPUs)")
+    ap.add_argument("--full", action="store_true",
+                    help="beside the device timing: its verification, the live rocprofv3 passes and the legs "
+                         "(cpu_baseline, e2e, configs), each unless its --no-... option is given; without --full "
+                         "none of them runs")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="write what the last timed step computed to DIR/<name>.npy (float32; indices float64), "
+                         "a seeded sample of whole stripes where the output is larger than the budget")
     return ap.parse_args()
+
+
+def plain_run(a):
+    """Without --full the run is the device timing alone: no verification
+    step, no profiler, no leg."""
+    if not a.full:
+        a.no_cpu = a.no_e2e = a.no_configs = a.no_prof = True
+    return a
 
 
 def box_of(pci_bus_id: str) -> dict:
@@ -434,10 +460,10 @@ DIST_ENV = ("RANK", "LOCAL_RANK", "WORLD_SIZE", "LOCAL_WORLD_SIZE", "GROUP_RANK"
 
 def workload_cmd(a) -> list:
     """This run's device workload alone (the PMC passes' child): a fresh
-    process, one rank, no legs, a few steps."""
+    process, one rank, no legs, a few steps and their verification."""
     cmd = [sys.executable, os.path.abspath(__file__), "--gpus", "1", "--mode", a.mode, "--stripes", str(a.stripes),
            "--nsrc", str(a.nsrc), "--chunk", str(a.chunk), "--rebuild-layout", a.rebuild_layout,
-           "--no-cpu", "--no-e2e", "--no-prof", "--no-configs", "--steps", "3", "--warmup", "1"]
+           "--full", "--no-cpu", "--no-e2e", "--no-prof", "--no-configs", "--steps", "3", "--warmup", "1"]
     for flag, val in (("--blocks-per-cu", a.blocks_per_cu), ("--vecs", a.vecs), ("--grid", a.grid)):
         if val:
             cmd += [flag, str(val)]
@@ -461,6 +487,60 @@ def mixed_lengths(stripes: int, N: int, C: int, rank: int) -> list:
         lens_all.append(ls)
         tot += int(ls.sum())
     return lens_all
+
+
+DUMP_BYTES = 48 << 20  # --dump-outputs: all ranks' out*.npy together (float32), index files aside
+
+
+def dump_sample(lengths: list, world: int) -> list:
+    """--dump-outputs: the stripes whose outputs are written -- all of them
+    where they fit a rank's share of DUMP_BYTES (one output byte is one
+    float32), else the first, the last and as many others in a fixed seeded
+    order as fit.  Ascending stripe indices; the same for every run of the
+    same workload."""
+    import numpy as np
+    budget = DUMP_BYTES // 4 // max(1, world)
+    if sum(lengths) <= budget:
+        return list(range(len(lengths)))
+    order = [0, len(lengths) - 1] + [int(i) + 1 for i in np.random.default_rng(11).permutation(len(lengths) - 2)]
+    pick, used = [], 0
+    for i in order:
+        if used + lengths[i] <= budget:
+            pick.append(i)
+            used += lengths[i]
+    return sorted(pick)
+
+
+def dump_outputs(dir_: str, q, rank: int, world: int, outs: list, fold16=None):
+    """--dump-outputs: what the last timed step left in the output buffer,
+    read back before anything else writes it.  outs: (device address, length)
+    of every stripe's output, in stripe order.  Files (numpy .npy; a
+    `_rank<r>` suffix in an N-rank job):
+      out.npy          float32, the sampled stripes' output bytes, concatenated
+      out_stripes.npy  float64, their stripe indices (dump_sample)
+      out_lengths.npy  float64, their lengths in bytes
+      out_fold.npy     float32[16], the XOR fold of the WHOLE output buffer to
+                       16 bytes (fold16: the device scratch that holds it)"""
+    import numpy as np
+    os.makedirs(dir_, exist_ok=True)
+    sfx = f"_rank{rank}" if world > 1 else ""
+    pick = dump_sample([n for _, n in outs], world)
+    got = np.empty(sum(outs[i][1] for i in pick), dtype=np.uint8)
+    off = 0
+    for i in pick:
+        ptr, n = outs[i]
+        if n:
+            q.d2h(got[off:off + n], ptr, n)
+        off += n
+    fold = np.empty(16, dtype=np.uint8)
+    if fold16 is not None:
+        q.d2h(fold, fold16, 16)
+    q.sync()
+    np.save(os.path.join(dir_, f"out{sfx}.npy"), got.astype(np.float32))
+    np.save(os.path.join(dir_, f"out_stripes{sfx}.npy"), np.asarray(pick, dtype=np.float64))
+    np.save(os.path.join(dir_, f"out_lengths{sfx}.npy"), np.asarray([outs[i][1] for i in pick], dtype=np.float64))
+    if fold16 is not None:
+        np.save(os.path.join(dir_, f"out_fold{sfx}.npy"), fold.astype(np.float32))
 
 
 def device_phase(a, rank: int, world: int, local_rank: int, coord) -> dict:
@@ -634,6 +714,26 @@ def device_phase(a, rank: int, world: int, local_rank: int, coord) -> dict:
         NS = N if (1 <= N <= 12 or N == 16) else 0  # widths without a specialisation run xor_stream<0, ...>
         kernel, kernel_tag = kernel.format(N=NS, U=U), kernel_tag.format(N=NS, U=U)
 
+    # --dump-outputs: the output buffer as the last timed step left it
+    if a.dump_outputs:
+        if a.mode == "mixed":
+            dump_outputs(a.dump_outputs, q, rank, world, [(x[0], x[1]) for x in stripes])
+        else:
+            q.xor_fold(out, S * C, chk + 32)
+            dump_outputs(a.dump_outputs, q, rank, world, [(out + i * C, C) for i in range(S)], fold16=chk + 32)
+
+    def result(verified):
+        device = eng.device
+        q.close()
+        eng.close()
+        return {"rank": rank, "world": world, "device": device, "bus_ids": bus_ids, "n_devices": n_devices,
+                "shared_gpu": shared_gpu, "cus": cus, "devname": devname, "S": S, "N": N, "C": C, "U": U,
+                "kernel": kernel, "kernel_tag": kernel_tag, "workload": workload, "bytes_per_step": bytes_per_step,
+                "wall": wall, "kern_ms": kern_ms, "seg_ms": seg_ms, "g": g, "verified": verified}
+
+    if not a.full:  # the timing alone: verified is None, not False
+        return result(None)
+
     # Verification after the timed region: clear the output, run ONE more
     # step, then check it on the device (fold conservation / rebuild compare)
     # and sampled stripes byte for byte against numpy (not the oracle).
@@ -686,13 +786,7 @@ def device_phase(a, rank: int, world: int, local_rank: int, coord) -> dict:
         verified = int(f.view("<u8")[0]) == 0 and sampled(
             idx, lambda i: [dget(src + (i * N + victim) * C, C)], lambda i: out + i * C, C)
 
-    device = eng.device
-    q.close()
-    eng.close()
-    return {"rank": rank, "world": world, "device": device, "bus_ids": bus_ids, "n_devices": n_devices,
-            "shared_gpu": shared_gpu, "cus": cus, "devname": devname, "S": S, "N": N, "C": C, "U": U,
-            "kernel": kernel, "kernel_tag": kernel_tag, "workload": workload, "bytes_per_step": bytes_per_step,
-            "wall": wall, "kern_ms": kern_ms, "seg_ms": seg_ms, "g": g, "verified": bool(verified)}
+    return result(bool(verified))
 
 
 def finish(a, d, dev: dict) -> tuple:
@@ -709,7 +803,8 @@ def finish(a, d, dev: dict) -> tuple:
     lens_all = mixed_lengths(a.stripes, N, C, d.rank) if a.mode == "mixed" and not a.no_cpu and d.rank == 0 else None
     wall_max = d.max(wall)
     total_bytes = d.sum(float(bytes_per_step * a.steps))
-    ok_all = d.sum(1.0 if verified else 0.0) == d.world
+    # a plain run (no --full) does not verify: None in the line, exit status 0
+    ok_all = d.sum(1.0 if verified else 0.0) == d.world if a.full else None
     kern_ms_max = d.max(kern_ms)
     # every rank's own figures (per-GPU rates of the N-GPU line): bus id, HIP-event
     # kernel time, its share of the wall clock
@@ -720,7 +815,7 @@ def finish(a, d, dev: dict) -> tuple:
                          "kernel_ms_max": round(max(seg_ms), 4),
                          "GiBps": round(bytes_per_step * a.steps / wall / GiB, 2),
                          "pct_hbm_peak": round(100.0 * bytes_per_step / (kern_ms * 1e-3) / 1e9 / HBM_PEAK_GBS, 2),
-                         "verified": bool(verified)})
+                         "verified": verified})
 
     # BASELINE config 1 end to end (rank 0; the reference's xor_parity as the
     # P-role fold beside the GPU fold and the pipeline, same store); first
@@ -841,13 +936,15 @@ def finish(a, d, dev: dict) -> tuple:
     else:
         line = None
     d.close()
-    return line, (0 if ok_all else 3)
+    return line, (3 if ok_all is False else 0)
 
 
 def main():
-    a = parse()
+    a = plain_run(parse())
     if a.gpus < 1:
         sys.exit("bench.py: --gpus must be >= 1")
+    if a.steps < 1:
+        sys.exit("bench.py: --steps must be >= 1")
     if a.device_helper:  # the profiled device helper (profiled_rank's child)
         rank, world, local_rank = (int(x) for x in a.device_helper.split(","))
         pc = PipeCoord()

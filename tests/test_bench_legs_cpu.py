@@ -159,7 +159,7 @@ def test_profiled_rank_patches_the_line(fake_rocprof, monkeypatch, capsys):
     profiled."""
     import bench
     from bcp_dist import Dist
-    monkeypatch.setattr(sys, "argv", ["bench.py", "--steps", "3", "--warmup", "1", "--no-e2e", "--no-cpu",
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--full", "--steps", "3", "--warmup", "1", "--no-e2e", "--no-cpu",
                                       "--no-configs"])
     a = bench.parse()
     a.stripes = 12_500
@@ -189,7 +189,7 @@ def test_profiled_rank_without_figures_times_in_process(fake_rocprof, monkeypatc
     import bench
     from bcp_dist import Dist
     monkeypatch.setenv("FAKE_ROCPROF_MODE", mode)  # no message at all / gone after its first collective
-    monkeypatch.setattr(sys, "argv", ["bench.py", "--steps", "3", "--warmup", "1", "--no-e2e", "--no-cpu",
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--full", "--steps", "3", "--warmup", "1", "--no-e2e", "--no-cpu",
                                       "--no-configs"])
     a = bench.parse()
     a.stripes = 64
@@ -218,7 +218,7 @@ def test_profiled_rank_helper_lost_midway_fails_an_n_rank_job(fake_rocprof, monk
         def close(self):
             pass
     monkeypatch.setenv("FAKE_ROCPROF_MODE", "midway")
-    monkeypatch.setattr(sys, "argv", ["bench.py", "--steps", "3", "--warmup", "1", "--no-e2e", "--no-cpu",
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--full", "--steps", "3", "--warmup", "1", "--no-e2e", "--no-cpu",
                                       "--no-configs"])
     a = bench.parse()
     a.stripes = 64
@@ -226,3 +226,34 @@ def test_profiled_rank_helper_lost_midway_fails_an_n_rank_job(fake_rocprof, monk
     out, err = capsys.readouterr()
     assert not [x for x in out.splitlines() if x.startswith("{")]
     assert "in the middle of the run" in err
+
+
+def test_dump_sample_is_fixed_and_fits_the_budget():
+    """--dump-outputs' stripes: all of them where they fit, else the first, the
+    last and a seeded choice of the others within the budget (shared by the
+    ranks), the same on every call."""
+    import bench
+    C = 512 * 1024
+    assert bench.dump_sample([C] * 24, 1) == list(range(24))
+    pick = bench.dump_sample([C] * 12_500, 1)
+    assert pick == bench.dump_sample([C] * 12_500, 1) == sorted(set(pick))
+    assert pick[0] == 0 and pick[-1] == 12_499 and len(pick) == bench.DUMP_BYTES // 4 // C == 24
+    assert len(bench.dump_sample([C] * 12_500, 8)) == 3
+    lens = [int(x.max()) for x in bench.mixed_lengths(64, 8, C, 0)]
+    pick = bench.dump_sample(lens, 1)
+    assert 0 in pick and len(lens) - 1 in pick and 4 * sum(lens[i] for i in pick) <= bench.DUMP_BYTES < 64e6
+
+
+def test_plain_run_switches_every_leg_off(monkeypatch):
+    """Without --full the legs, the profiler and the verification are off
+    whatever else the command line says; --full leaves each to its own option."""
+    import bench
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--gpus", "1", "--steps", "7", "--warmup", "2"])
+    a = bench.plain_run(bench.parse())
+    assert (a.full, a.no_cpu, a.no_e2e, a.no_configs, a.no_prof) == (False, True, True, True, True)
+    assert (a.steps, a.warmup, a.dump_outputs) == (7, 2, None)
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--full", "--no-e2e", "--dump-outputs", "d"])
+    a = bench.plain_run(bench.parse())
+    assert (a.full, a.no_cpu, a.no_e2e, a.no_configs, a.no_prof) == (True, False, True, False, False)
+    assert a.dump_outputs == "d"
+    assert "--full" in bench.workload_cmd(a)  # the PMC passes' child verifies its steps as before

@@ -76,14 +76,23 @@ def _hook_so(tmp_path):
     return so
 
 
+def socket_in(tmp_path, monkeypatch):
+    """The socket's path as the server and the clients are given it: relative
+    to tmp_path, which becomes the working directory of the test and of the
+    processes it starts -- a Unix socket's address holds at most 107 bytes,
+    and a temporary directory's full path can be longer than that."""
+    monkeypatch.chdir(tmp_path)
+    return "fs.sock"
+
+
 @pytest.mark.timeout(240)
 @pytest.mark.parametrize("fold", ["pipelined", "batched"])
-def test_connected_clients_fold_through_the_server(tmp_path, fold):
+def test_connected_clients_fold_through_the_server(tmp_path, monkeypatch, fold):
     """Two client processes (loopback ranks inside each) on one server, 3
     connections each: every window the clients' P roles fold goes to the
     server, which maps each client's memfd arena at its own address."""
     so = _hook_so(tmp_path)
-    sock = str(tmp_path / "fs.sock")
+    sock = socket_in(tmp_path, monkeypatch)
     srv = subprocess.Popen([sys.executable, "-c", SERVER, sock, ROOT, "6", "hook", so], stdout=subprocess.PIPE,
                            text=True)
     assert srv.stdout.readline().strip() == "serving"
@@ -109,12 +118,12 @@ def test_connected_clients_fold_through_the_server(tmp_path, fold):
 
 
 @pytest.mark.timeout(120)
-def test_client_without_a_server_fails_tasks_not_the_run(tmp_path):
+def test_client_without_a_server_fails_tasks_not_the_run(tmp_path, monkeypatch):
     """The server accepts the client's connections and exits at once (it was
     told to serve 0 requests by closing them): the client's folds fail, its
     ranks raise the sticky error, and the run returns."""
     so = _hook_so(tmp_path)
-    sock = str(tmp_path / "fs.sock")
+    sock = socket_in(tmp_path, monkeypatch)
     # a "server" that accepts and closes every connection
     import socket
     import threading

@@ -38,7 +38,7 @@ def _run(cmd, timeout):
 @pytest.mark.timeout(400)
 @pytest.mark.parametrize("mode", ["gen", "rebuild", "mixed"])
 def test_bench_one_rank_small(bcp, mode):
-    line = _run([sys.executable, "bench.py", "--stripes", "64", "--steps", "5", "--warmup", "1", "--no-cpu",
+    line = _run([sys.executable, "bench.py", "--full", "--stripes", "64", "--steps", "5", "--warmup", "1", "--no-cpu",
                  "--no-e2e", "--no-prof", "--no-configs", "--mode", mode], 300)
     assert line["config"]["verified_on_device"] is True
     assert line["n_gpus"] == 1 and line["config"]["ranks"] == 1 and line["config"]["shared_gpu"] is False
@@ -56,7 +56,7 @@ def test_bench_torchrun_two_ranks_labels(bcp):
     ndev = bcp.device_count()
     line = _run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2",
                  "--master-addr", "127.0.0.1", "--master-port", str(_free_port()),
-                 "bench.py", "--gpus", "2", "--stripes", "64", "--steps", "2", "--warmup", "1", "--no-cpu",
+                 "bench.py", "--full", "--gpus", "2", "--stripes", "64", "--steps", "2", "--warmup", "1", "--no-cpu",
                  "--no-e2e", "--no-prof", "--no-configs", "--allow-shared"], 420)
     assert line["config"]["verified_on_device"] is True
     assert line["config"]["ranks"] == 2
@@ -78,7 +78,7 @@ def test_bench_gpus_n_launches_its_own_ranks(bcp, n):
     ndev = bcp.device_count()
     env = dict(os.environ, MASTER_ADDR="127.0.0.1")
     env.pop("WORLD_SIZE", None)
-    args = [sys.executable, "bench.py", "--gpus", str(n), "--stripes", "64", "--steps", "2", "--warmup", "1",
+    args = [sys.executable, "bench.py", "--full", "--gpus", str(n), "--stripes", "64", "--steps", "2", "--warmup", "1",
             "--cpu-seconds", "1", "--cpu-stripes", "16", "--e2e-gib", "0.1" if n == 8 else "0.25", "--e2e-reps", "1",
             "--c1-files", "48", "--c1-reps", "1", "--c5-reps", "1"]
     args += [] if n == 2 else ["--no-prof"]  # the live profile from rank 0 of an N-rank job
@@ -134,8 +134,9 @@ def test_bench_gpus_n_launches_its_own_ranks(bcp, n):
 def test_bench_mixed_line_carries_cpu_baseline_and_e2e(bcp):
     """Mixed mode (config-5 shapes): the reference's fold timed over the same
     zero-padded stripe shapes, and the end-to-end leg, in the one-rank line."""
-    line = _run([sys.executable, "bench.py", "--mode", "mixed", "--stripes", "64", "--steps", "2", "--warmup", "1",
-                 "--cpu-seconds", "1", "--e2e-gib", "0.25", "--e2e-reps", "1", "--no-prof", "--no-configs"], 300)
+    line = _run([sys.executable, "bench.py", "--full", "--mode", "mixed", "--stripes", "64", "--steps", "2",
+                 "--warmup", "1", "--cpu-seconds", "1", "--e2e-gib", "0.25", "--e2e-reps", "1", "--no-prof",
+                 "--no-configs"], 300)
     cpu = line["cpu_baseline"]
     assert cpu["kind"] == "reference" and cpu["value"] > 0 and "stripe_shapes" in cpu["legs"][0]
     assert line["e2e"]["gen"]["verified"] is True and line["e2e"]["rebuild"]["verified"] is True
@@ -149,7 +150,7 @@ def test_bench_configs_block_one_rank(bcp):
     reference's own xor_parity as the P-role fold, with the GPU fold and
     through the pipeline, gen and rebuild, all verified; config 5's changelog
     subset planned against the DB and recomputed, verified."""
-    line = _run([sys.executable, "bench.py", "--stripes", "64", "--steps", "2", "--warmup", "1", "--no-prof",
+    line = _run([sys.executable, "bench.py", "--full", "--stripes", "64", "--steps", "2", "--warmup", "1", "--no-prof",
                  "--cpu-seconds", "1", "--e2e-gib", "0.25", "--e2e-reps", "1", "--c1-files", "96",
                  "--c1-reps", "1", "--c5-reps", "1"], 360)
     c1 = line["configs"]["config1"]
@@ -190,8 +191,9 @@ def test_bench_line_survives_an_e2e_failure_on_one_rank(bcp):
     prints the device line with the failure reported inside `e2e`."""
     env = dict(os.environ, MASTER_ADDR="127.0.0.1", BCP_BENCH_E2E_FAIL_RANK="1")
     env.pop("WORLD_SIZE", None)
-    r = subprocess.run([sys.executable, "bench.py", "--gpus", "2", "--allow-shared", "--stripes", "64", "--steps", "2",
-                        "--warmup", "1", "--no-cpu", "--e2e-gib", "0.25", "--e2e-reps", "1", "--no-prof", "--no-configs"],
+    r = subprocess.run([sys.executable, "bench.py", "--full", "--gpus", "2", "--allow-shared", "--stripes", "64",
+                        "--steps", "2", "--warmup", "1", "--no-cpu", "--e2e-gib", "0.25", "--e2e-reps", "1",
+                        "--no-prof", "--no-configs"],
                        cwd=ROOT, env=env, capture_output=True, text=True, timeout=360)
     assert r.returncode == 0, (r.returncode, r.stdout[-2000:], r.stderr[-4000:])
     line = _last_json(r.stdout)
@@ -211,8 +213,8 @@ def test_bench_live_profile_on_its_own_box(bcp, mode):
     and compared with the same process's HIP events over the same launches;
     then the two PMC passes of the workload (traffic within 1 % of the
     algorithmic bytes), same_box set."""
-    line = _run([sys.executable, "bench.py", "--mode", mode, "--stripes", "256", "--steps", "4", "--warmup", "2",
-                 "--no-cpu", "--no-e2e", "--no-configs"], 450)
+    line = _run([sys.executable, "bench.py", "--full", "--mode", mode, "--stripes", "256", "--steps", "4",
+                 "--warmup", "2", "--no-cpu", "--no-e2e", "--no-configs"], 450)
     rf = line["roofline"]
     live = rf["live_profile"]
     assert live and "error" not in live and "pmc_error" not in live, live
@@ -237,8 +239,8 @@ def test_bench_line_survives_failed_legs(bcp):
     config 1, config 5 through the protocol -- the line is printed, verified,
     with each failure in its own block and the e2e block intact."""
     env = dict(os.environ, BCP_BENCH_FAIL_LEG="cpu_baseline,config1,config5_protocol")
-    r = subprocess.run([sys.executable, "bench.py", "--stripes", "64", "--steps", "2", "--warmup", "1", "--no-prof",
-                        "--cpu-seconds", "1", "--e2e-gib", "0.25", "--e2e-reps", "1"], cwd=ROOT, env=env,
+    r = subprocess.run([sys.executable, "bench.py", "--full", "--stripes", "64", "--steps", "2", "--warmup", "1",
+                        "--no-prof", "--cpu-seconds", "1", "--e2e-gib", "0.25", "--e2e-reps", "1"], cwd=ROOT, env=env,
                        capture_output=True, text=True, timeout=420)
     assert r.returncode == 0, (r.returncode, r.stdout[-2000:], r.stderr[-4000:])
     line = _last_json(r.stdout)
@@ -248,3 +250,35 @@ def test_bench_line_survives_failed_legs(bcp):
     assert "injected" in line["configs"]["config5_protocol"]["error"]
     assert line["e2e"]["gen"]["verified"] is True and line["e2e"]["errors"] is None
     assert line["configs"]["config5_partial"]["verified"] is True
+
+
+@pytest.mark.timeout(120)
+def test_bench_plain_run_times_only_and_dumps_its_outputs(bcp, oracle, tmp_path):
+    """The driver's plain form (no --full): the device timing alone -- no
+    verification step, no profiler, no leg -- with the headline fields, and
+    --dump-outputs: the parity the last timed step computed, every stripe at
+    this size, byte for byte the XOR of the seeded inputs (numpy), its 16-byte
+    fold, and the same files from a second run."""
+    import numpy as np
+    S, N, C = 24, 8, 512 * 1024
+    dirs = [tmp_path / "a", tmp_path / "b"]
+    for d in dirs:
+        line = _run([sys.executable, "bench.py", "--gpus", "1", "--steps", "3", "--warmup", "1", "--stripes", str(S),
+                     "--dump-outputs", str(d)], 100)
+        assert line["steps"] == 3 and line["warmup"] == 1 and line["ms_per_step"] > 0 and line["value"] > 0
+        assert line["unit"] == "GiB/s" and line["higher_is_better"] is True and line["dtype"] == "u8"
+        assert line["value"] == pytest.approx(S * (N + 1) * C / 2**30 / (line["ms_per_step"] * 1e-3), rel=5e-3)
+        assert len(line["roofline"]["kernel_ms_steps"]) == 3 and line["roofline"]["frac"] > 0
+        assert line["config"]["verified_on_device"] is None and line["per_rank"][0]["verified"] is None
+        assert line["cpu_baseline"] is None and line["e2e"] is None and line["configs"]["config1"] is None
+        assert line["roofline"]["live_profile"] is None and line["roofline"]["profiled_in_process"] is False
+    src = oracle.synthetic(S * N * C, 1).reshape(S, N, C)
+    want = np.bitwise_xor.reduce(src, axis=1)
+    got = {n: np.load(dirs[0] / f"{n}.npy") for n in ("out", "out_stripes", "out_lengths", "out_fold")}
+    assert got["out"].dtype == np.float32 and got["out_fold"].dtype == np.float32
+    assert got["out_stripes"].dtype == got["out_lengths"].dtype == np.float64
+    assert np.array_equal(got["out_stripes"], np.arange(S)) and np.array_equal(got["out_lengths"], np.full(S, C))
+    assert np.array_equal(got["out"], want.reshape(-1).astype(np.float32))
+    assert np.array_equal(got["out_fold"], np.bitwise_xor.reduce(want.reshape(-1, 16), axis=0).astype(np.float32))
+    for n, x in got.items():
+        assert np.array_equal(np.load(dirs[1] / f"{n}.npy"), x), n

@@ -732,7 +732,7 @@ def test_pipeline_rebuild_matches_protocol_rebuild(bcp, oracle, tmp_path):
 
 
 @pytest.mark.parametrize("fold", ["pipelined", "batched"])
-def test_node_fold_server_for_connected_clients(tmp_path, fold):
+def test_node_fold_server_for_connected_clients(tmp_path, monkeypatch, fold):
     """The node fold server as an MPI job would use it: a server process on a
     Unix socket holds the GPU (bcp_fold_server_serve); two client processes
     connect (bcp_fold_server_connect, memfd arenas the server maps at its own
@@ -743,7 +743,7 @@ def test_node_fold_server_for_connected_clients(tmp_path, fold):
     import sys
     import time
     import test_fold_server_cpu as F
-    sock = str(tmp_path / "fs.sock")
+    sock = F.socket_in(tmp_path, monkeypatch)
     srv = subprocess.Popen([sys.executable, "-c", F.SERVER, sock, F.ROOT, "6", "gpu", ""], stdout=subprocess.PIPE,
                            text=True)
     assert srv.stdout.readline().strip() == "serving"

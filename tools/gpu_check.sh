@@ -17,6 +17,6 @@ if [ -z "$NO_STRESS" ]; then
     > $O/pool_switch.jsonl 2> $O/pool_switch.err || { echo STRESS_FAIL; tail -5 $O/pool_switch.jsonl; exit 1; }
   tail -1 $O/pool_switch.jsonl
 fi
-timeout -k 10 300 python -u bench.py > $O/bench.json 2> $O/bench.err || { echo BENCH_FAIL; exit 1; }
+timeout -k 10 300 python -u bench.py --full > $O/bench.json 2> $O/bench.err || { echo BENCH_FAIL; exit 1; }
 cat $O/bench.json
 echo ALL_OK

@@ -19,7 +19,7 @@ for m in gen rebuild mixed config4; do
   [ $m = config4 ] && args="--mode gen --stripes 15625"
   [ $m != gen ] && args="$args --no-cpu --no-e2e --no-configs"
   mkdir -p $O/$m
-  timeout -k 10 600 python3 $R/bench.py $args --profile-dir $O/$m > $O/$m/bench.json 2> $O/$m/bench.err || { echo BENCH_${m}_FAIL; exit 1; }
+  timeout -k 10 600 python3 $R/bench.py --full $args --profile-dir $O/$m > $O/$m/bench.json 2> $O/$m/bench.err || { echo BENCH_${m}_FAIL; exit 1; }
   [ $m = gen ] && cp $O/gen/bench.json $O/bench_gen.json
   echo PROF_${m}_OK
 done
