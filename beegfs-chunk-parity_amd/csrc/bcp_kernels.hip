@@ -413,6 +413,10 @@ __device__ __noinline__ void desc_tile_general(const DescBatch &b, uint32_t stri
   const_as<bcp_source> *srcs = cst(b.sources) + first_src;
   const uint32_t nsrc = dp_->nsrc;
   const uint64_t out_len = dp_->out_len, window = dp_->window;
+  // The replayed stream ends with the longest source (the reference writes
+  // max_cs bytes of it): output bytes from there on are zero, as without a
+  // window.  The staged run is sorted longest first.
+  const uint64_t max_cs = window && nsrc ? srcs[0].len : ~0ull;
   glob<unsigned char> *dp = gp<unsigned char>(dp_->dst);
   const uint64_t lane_off = (uint64_t)tile * b.tile_bytes +
                             (uint64_t)((threadIdx.x >> 6) * (64u * U) + (threadIdx.x & 63u)) * 16u;
@@ -421,10 +425,18 @@ __device__ __noinline__ void desc_tile_general(const DescBatch &b, uint32_t stri
     const uint64_t off = lane_off + (uint64_t)u * 1024u;
     if (off >= out_len) break;
     v4u x = zero4();
-    for (uint32_t k = 0; k < nsrc; k++) {
-      const uint64_t len = srcs[k].len;
-      const uint64_t o = window ? replay_offset(off, len, window) : off;
-      x ^= load_src_tail(gp<const unsigned char>(srcs[k].ptr), len, o);
+    if (off < max_cs) {
+      for (uint32_t k = 0; k < nsrc; k++) {
+        const uint64_t len = srcs[k].len;
+        const uint64_t o = window ? replay_offset(off, len, window) : off;
+        x ^= load_src_tail(gp<const unsigned char>(srcs[k].ptr), len, o);
+      }
+      if (max_cs - off < 16) {  // the stream ends inside this vector
+        const uint32_t keep = (uint32_t)(max_cs - off);
+#pragma unroll
+        for (uint32_t i = 0; i < 16; i++)
+          if (i >= keep) x[i >> 2] &= ~(0xFFu << (8 * (i & 3)));
+      }
     }
     store_tail(dp, out_len, off, x);
   }
@@ -698,17 +710,21 @@ __device__ __forceinline__ void write_tile(const DescBatch &b, uint32_t s, const
     // ptr + mapped offset (its last readable window re-sent for every later
     // window) -- a plain tile with per-source addresses.  Covering sources
     // first, then the ones ending inside the tile; more than kTileSrcs
-    // reaching in falls back to the general path.
+    // reaching in falls back to the general path.  The replayed stream ends
+    // with the longest source (run[0]: the run is sorted): from there on the
+    // output is zero, so no source reaches past it.
     const uint64_t w = off / d.window;
+    const uint64_t max_cs = d.nsrc ? run[0].len : 0;
+    const uint64_t left = max_cs > off ? max_cs - off : 0;
     uint32_t nf = 0, na = 0;
     for (int pass = 0; pass < 2; pass++)
       for (uint32_t k = 0; k < d.nsrc; k++) {
         const uint64_t len = run[k].len;
-        if (len == 0) continue;
+        if (len == 0 || left == 0) continue;
         const uint64_t lw = (len - 1) / d.window;
         const uint64_t mo = w > lw ? off - (w - lw) * d.window : off;
         if (len <= mo) continue;
-        const uint64_t eff = len - mo;
+        const uint64_t eff = len - mo < left ? len - mo : left;
         if ((pass == 0) != (eff >= T)) continue;
         if (na < (uint32_t)kTileSrcs) {
           rec.src[na] = run[k].ptr + mo;

@@ -30,6 +30,8 @@
  * with last readable window lw_k = (len_k - 1) / W and w > lw_k replays
  * window lw_k (chunk_sender never refills its buffer after EOF,
  * task_processing.c:291-308, quirk A3-q1).  len_k = 0 always reads zeros.
+ * The replayed stream ends with the longest source, as the reference's parity
+ * body does: with a window, out[j] = 0 for j >= max_k len_k.
  */
 #ifndef BCP_H
 #define BCP_H

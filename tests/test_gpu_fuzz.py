@@ -3,7 +3,8 @@ for a time budget (BCP_FUZZ_SECONDS, default 8 s; a longer soak is the same
 test with a larger budget).  Each round draws a batch -- widths 1..56, lengths
 from 0 B to 4 MiB (tiny, unaligned, exact 16-byte multiples, tile-sized),
 misaligned sources and outputs, missing sources, rebuild truncation
-(out_len below the longest source), window replay (quirk A3-q1) -- and the
+(out_len below the longest source), outputs longer than every source (a
+zero tail), window replay (quirk A3-q1) -- and the
 engine's tuning (tile sizes of both kernels, the argument form on or off,
 tables read from host or device memory), so every path of the engine takes
 part: xor_stream's pointer-table form for uniform batches, xor_desc_args for
@@ -17,6 +18,7 @@ import time
 import numpy as np
 import pytest
 
+from devbuf import GuardError
 from test_gpu_xor import Dev, gpu_stripes  # noqa: F401  (helpers of the device tests)
 
 pytestmark = pytest.mark.gpu
@@ -41,8 +43,10 @@ def _length(rng, big):
     return int(rng.integers(1, big + 1))                     # anything (unaligned)
 
 
-def _batch(rng, budget_bytes):
-    """A list of stripe dicts for gpu_stripes and their expected outputs."""
+def _batch(rng, budget_bytes, xrng):
+    """A list of stripe dicts for gpu_stripes and their expected outputs.
+    xrng: a second generator for the zero-tail draw, so that a seed's sources
+    and every other draw stay what they were before that draw existed."""
     from oracle import gen_parity_file, xor_padded_np
     stripes, refs, used = [], [], 0
     uniform = rng.random() < 0.2
@@ -68,6 +72,10 @@ def _batch(rng, budget_bytes):
             st["window"] = window
         elif not uniform and m and rng.random() < 0.2:
             st["out_len"] = int(rng.integers(1, m + 1))       # rebuild truncation
+        elif not uniform and xrng.random() < 0.15:
+            # an output longer than every source: a tail of zero padding only
+            # (bytes, whole vectors, whole tiles) that the kernel must still store
+            st["out_len"] = m + max(1, _length(xrng, 128 * KiB))
         if not uniform:
             st["pads"] = [int(x) for x in rng.integers(0, 16, size=n)]
             st["dst_pad"] = int(rng.integers(0, 16))
@@ -87,7 +95,7 @@ def _batch(rng, budget_bytes):
 def test_random_batches_match_the_oracle(oracle, engine, queue):
     budget = float(os.environ.get("BCP_FUZZ_SECONDS", "8"))
     seed = int(os.environ.get("BCP_FUZZ_SEED", "2026"))
-    rng = np.random.default_rng(seed)
+    rng, xrng = np.random.default_rng(seed), np.random.default_rng([seed, 1])
     defaults = {k: engine.option(k) for k in TUNING}
     t_end = time.monotonic() + budget
     rounds = stripes_done = bytes_done = 0
@@ -97,12 +105,15 @@ def test_random_batches_match_the_oracle(oracle, engine, queue):
             tuning = {k: (v[0] if rng.random() < 0.5 else v[int(rng.integers(0, len(v)))]) for k, v in TUNING.items()}
             for k, v in tuning.items():
                 engine.option(k, v)
-            stripes, refs = _batch(rng, 48 * MiB)
+            stripes, refs = _batch(rng, 48 * MiB, xrng)
             dev = Dev(engine, queue)
             try:
-                outs = gpu_stripes(dev, queue, stripes)
-            finally:
-                dev.free()
+                try:
+                    outs = gpu_stripes(dev, queue, stripes)
+                finally:
+                    dev.free()
+            except GuardError as e:  # a store outside an output (the destination area or a buffer's guards)
+                pytest.fail(f"seed {seed} round {rounds} tuning {tuning}: {e}")
             forms.add(engine.option("last_desc_form"))
             for i, (o, r) in enumerate(zip(outs, refs)):
                 if not np.array_equal(o, r):

@@ -30,29 +30,77 @@ def expect(oracle, chunks, out_len):
     return oracle.xor_parity(data.reshape(-1), out_len, n)[:out_len]
 
 
+GAP = 256  # poison bytes between the arena's blocks
+
+
 class Arena:
-    """Mapped pinned host memory carved into source and output blocks."""
+    """Mapped pinned host memory carved into source and output blocks.
+
+    Every block handed out, and a gap of at least GAP bytes before and after
+    it, holds random non-zero poison (drawn per arena; zero or a constant
+    could hide a load past a row's end: two rows reading the same constant
+    cancel), so no block starts where another ends and an output never starts
+    out as zeros.  The arena records which ranges are outputs; snapshot() and
+    check_untouched() show that a fold changed nothing else."""
+
+    _arenas = 0
 
     def __init__(self, eng, nbytes):
         self.eng, self.n = eng, nbytes
         self.base = eng.host_alloc(nbytes, mapped=True)
         self.view = host_view(self.base, nbytes)
         self.off = 0
+        self.outputs = []  # (offset, length) of the blocks handed out as outputs
+        Arena._arenas += 1
+        self.rng = np.random.default_rng(0xA7E4A + Arena._arenas)
+        self.pattern = self.rng.integers(1, 256, size=1 * MiB + 4099, dtype=np.uint8)
 
-    def take(self, n, align=16, skew=0):
-        self.off = (self.off + align - 1) // align * align + skew
-        assert self.off + n <= self.n
-        a = self.base + self.off
-        self.off += n
-        return a
+    def _poison(self, lo, hi):
+        """Gaps: fresh draws.  Blocks: the arena's pattern from a random phase (they are mostly overwritten)."""
+        if hi - lo <= 4 * GAP:
+            self.view[lo:hi] = self.rng.integers(1, 256, size=hi - lo, dtype=np.uint8)
+        else:
+            ph = int(self.rng.integers(0, self.pattern.size // 2))
+            self.view[lo:hi] = np.resize(self.pattern[ph:], hi - lo)
+
+    def take(self, n, align=16, skew=0, output=True):
+        """A block of n bytes (an output unless told otherwise)."""
+        start = (self.off + GAP + align - 1) // align * align + skew
+        assert start + n + GAP <= self.n
+        self._poison(self.off, start)
+        self._poison(start, start + n)
+        self._poison(start + n, start + n + GAP)
+        self.off = start + n
+        if output:
+            self.outputs.append((start, n))
+        return self.base + start
 
     def put(self, arr, align=16, skew=0):
-        a = self.take(len(arr), align, skew)
+        a = self.take(len(arr), align, skew, output=False)
         self.view[a - self.base:a - self.base + len(arr)] = arr
         return a
 
     def get(self, addr, n):
         return self.view[addr - self.base:addr - self.base + n].copy()
+
+    def snapshot(self):
+        """The used prefix (and the gap after it), to be taken before the submissions."""
+        return self.view[:self.off + GAP].copy()
+
+    def check_untouched(self, snap):
+        """Nothing outside the recorded outputs changed since the snapshot:
+        rows, gaps and earlier blocks are as they were."""
+        diff = self.view[:snap.size] != snap
+        for o, n in self.outputs:
+            diff[o:o + n] = False
+        w = np.flatnonzero(diff)
+        if w.size:
+            at = int(w[0])
+            near = min(self.outputs, key=lambda r: min(abs(at - r[0]), abs(at - (r[0] + r[1]))), default=(0, 0))
+            raise AssertionError(f"{w.size} arena bytes outside every output changed, first at offset {at} "
+                                 f"(0x{int(snap[at]):02x} -> 0x{int(self.view[at]):02x}); nearest output "
+                                 f"[{near[0]}, {near[0] + near[1]}): {at - near[0]} bytes from its start, "
+                                 f"{at - near[0] - near[1]} from its end")
 
     def close(self):
         self.eng.host_free(self.base)
@@ -85,6 +133,7 @@ def test_ring_folds_host_rows_from_many_threads(bcp, engine, arena, oracle):
     rng = np.random.default_rng(7)
     cases = [random_stripe(rng, arena, int(rng.choice([4 * KiB, 64 * KiB, 512 * KiB, 1536 * KiB])))
              for _ in range(96)]
+    snap = arena.snapshot()
     ring = bcp.Ring(engine)
     try:
         def one(c):
@@ -94,6 +143,7 @@ def test_ring_folds_host_rows_from_many_threads(bcp, engine, arena, oracle):
 
         with cf.ThreadPoolExecutor(12) as ex:
             outs = list(ex.map(one, cases))
+        arena.check_untouched(snap)
         for (chunks, _, _, out_len), got in zip(cases, outs):
             np.testing.assert_array_equal(got, expect(oracle, chunks, out_len))
         pieces, launches = ring.stats()
@@ -108,7 +158,7 @@ def test_ring_wide_and_ragged_stripes(bcp, engine, arena, oracle):
     rng = np.random.default_rng(11)
     ring = bcp.Ring(engine, workers=16)
     try:
-        cases, handles = [], []
+        cases = []
         for n, out_len, lens in [
             (56, 100 * KiB + 3, None),
             (13, 2 * MiB + 17, None),
@@ -122,14 +172,79 @@ def test_ring_wide_and_ragged_stripes(bcp, engine, arena, oracle):
             chunks = [rng.integers(0, 256, size=L, dtype=np.uint8) for L in lens]
             srcs = [(arena.put(c, skew=int(rng.integers(0, 16))), len(c)) for c in chunks]
             dst = arena.take(out_len, skew=int(rng.integers(0, 16)))
-            cases.append((chunks, dst, out_len))
-            handles.append(ring.submit(dst, out_len, srcs))
+            cases.append((chunks, dst, out_len, srcs))
+        snap = arena.snapshot()
+        handles = [ring.submit(dst, out_len, srcs) for _, dst, out_len, srcs in cases]
         for h in handles:
             ring.wait(h)
-        for chunks, dst, out_len in cases:
+        arena.check_untouched(snap)
+        for chunks, dst, out_len, _ in cases:
             np.testing.assert_array_equal(arena.get(dst, out_len), expect(oracle, chunks, out_len))
     finally:
         ring.close()
+
+
+PIECE, TILE = 512 * KiB, 32 * KiB  # the ring's cuts: pieces of a stripe, ~32 KiB parts of a piece
+
+
+def ring_cuts(out_len):
+    """Where the ring cuts a stripe (to choose lengths around them; the
+    expected bytes never use this): pieces of 512 KiB, each split into
+    parts = ceil(len / 32 KiB) tiles of ceil(len / parts) rounded up to 4 KiB."""
+    cuts = []
+    for p0 in range(0, out_len, PIECE):
+        plen = min(PIECE, out_len - p0)
+        parts = -(-plen // TILE)
+        tb = (-(-plen // parts) + 4095) // 4096 * 4096
+        if p0:
+            cuts.append(p0)
+        cuts += [p0 + j * tb for j in range(1, parts) if j * tb < plen]
+    return cuts
+
+
+EDGE_OUT_LENS = [4095, 4096, 4097, 32 * KiB - 1, 32 * KiB, 32 * KiB + 1, 36 * KiB + 1, 512 * KiB - 1, 512 * KiB,
+                 512 * KiB + 1, 544 * KiB + 1, 1 * MiB + 15]
+
+
+@pytest.mark.parametrize("skewed", [False, True], ids=["aligned", "skewed"])
+def test_ring_piece_and_part_edges(bcp, engine, arena, oracle, skewed):
+    """Output lengths at the ring's cuts (one 4 KiB vector row, one part, one
+    piece, and one byte or one part past each), sources that end at 0, 1,
+    out_len, out_len - 1 / - 16 / - 17, past out_len (truncated), and on a
+    part or piece boundary exactly and one byte to either side, at widths
+    around the fold's groups of four sources; aligned, and with the output and
+    every source skewed by 1..15 bytes.  One worker; expected bytes from the
+    oracle's xor_parity over the zero-padded rows."""
+    rng = np.random.default_rng(2100 + skewed)
+    cases = []
+    for out_len in EDGE_OUT_LENS:
+        cuts = ring_cuts(out_len)
+        near = sorted({cuts[0], cuts[len(cuts) // 2], cuts[-1]}) if cuts else []
+        cand = [0, 1, out_len, out_len - 1, out_len - 16, out_len - 17, out_len + 100]
+        cand += [c + d for c in near for d in (0, -1, 1)]
+        turn = 0
+        for n in (1, 4, 5, 8, 9):
+            lens = [cand[(turn + k) % len(cand)] for k in range(n)]  # every candidate, in turn
+            turn += n
+            chunks = [rng.integers(1, 256, size=L, dtype=np.uint8) for L in lens]
+            skew = (lambda: int(rng.integers(1, 16))) if skewed else (lambda: 0)
+            srcs = [(arena.put(c, skew=skew()), len(c)) for c in chunks]
+            dst = arena.take(out_len, skew=skew())
+            cases.append((chunks, srcs, dst, out_len))
+    snap = arena.snapshot()
+    ring = bcp.Ring(engine, workers=1)
+    try:
+        handles = [ring.submit(dst, out_len, srcs) for _, srcs, dst, out_len in cases]
+        for h in handles:
+            ring.wait(h)
+    finally:
+        ring.close()
+    arena.check_untouched(snap)
+    for chunks, _, dst, out_len in cases:
+        got, want = arena.get(dst, out_len), expect(oracle, chunks, out_len)
+        if not np.array_equal(got, want):
+            w = np.flatnonzero(got != want)
+            pytest.fail(f"out_len {out_len} lens {[len(c) for c in chunks]}: {w.size} bytes differ, first at {w[0]}")
 
 
 def test_ring_device_memory_and_reuse_past_ring_size(bcp, engine, queue, oracle):
@@ -170,9 +285,11 @@ def test_ring_launch_idles_out_and_comes_back(bcp, engine, arena, oracle):
     try:
         for burst in range(4):
             cases = [random_stripe(rng, arena, 64 * KiB) for _ in range(10)]
+            snap = arena.snapshot()
             hs = [ring.submit(d, n, s) for _, s, d, n in cases]
             for h in hs:
                 ring.wait(h)
+            arena.check_untouched(snap)
             for chunks, _, d, n in cases:
                 np.testing.assert_array_equal(arena.get(d, n), expect(oracle, chunks, n))
             time.sleep(0.03)
@@ -180,9 +297,11 @@ def test_ring_launch_idles_out_and_comes_back(bcp, engine, arena, oracle):
         assert launches >= 4, (pieces, launches)
         # a waiter alone (no submit after the close) must also get its ticket
         chunks, srcs, d, n = random_stripe(rng, arena, 64 * KiB)
+        snap = arena.snapshot()
         h = ring.submit(d, n, srcs)
         while not ring.query(h):
             pass
+        arena.check_untouched(snap)
         np.testing.assert_array_equal(arena.get(d, n), expect(oracle, chunks, n))
     finally:
         t0 = time.perf_counter()

@@ -10,42 +10,11 @@ import os
 import numpy as np
 import pytest
 
+from devbuf import FILL, Dev, assert_stripes_equal, gpu_stripes  # noqa: F401  (test_gpu_fuzz imports Dev and gpu_stripes from here)
+
 pytestmark = pytest.mark.gpu
 GOLD = json.load(open(os.path.join(os.path.dirname(__file__), "golden", "kats.json")))
 KiB, MiB = 1024, 1024 * 1024
-
-
-class Dev:
-    """Scratch device allocations freed at test end."""
-
-    def __init__(self, eng, q):
-        self.eng, self.q, self.ptrs = eng, q, []
-
-    def alloc(self, n):
-        p = self.eng.alloc(max(n, 16))
-        self.ptrs.append(p)
-        return p
-
-    def put(self, arr, pad=0):
-        """Upload arr at byte offset `pad` inside a fresh allocation; returns device address."""
-        arr = np.ascontiguousarray(arr, dtype=np.uint8)
-        base = self.alloc(arr.size + pad + 16)
-        if arr.size:
-            self.q.h2d(base + pad, arr)
-        return base + pad
-
-    def get(self, ptr, n):
-        out = np.empty(max(n, 1), dtype=np.uint8)
-        if n:
-            self.q.d2h(out, ptr, n)
-        self.q.sync()
-        return out[:n]
-
-    def free(self):
-        self.q.sync()
-        for p in self.ptrs:
-            self.eng.free(p)
-        self.ptrs = []
 
 
 @pytest.fixture
@@ -53,25 +22,6 @@ def dev(engine, queue):
     d = Dev(engine, queue)
     yield d
     d.free()
-
-
-def gpu_stripes(dev, queue, stripes):
-    """stripes: list of dict(chunks=[np arrays or None], out_len, window, pads) -> list of outputs."""
-    descs, sources, outs = [], [], []
-    for st in stripes:
-        pads = st.get("pads") or [0] * len(st["chunks"])
-        first = len(sources)
-        for c, pad in zip(st["chunks"], pads):
-            if c is None or len(c) == 0:
-                sources.append((0, 0))
-            else:
-                sources.append((dev.put(c, pad), len(c)))
-        dptr = dev.alloc(st["out_len"] + 32) + st.get("dst_pad", 0)
-        outs.append((dptr, st["out_len"]))
-        descs.append((dptr, st["out_len"], first, len(st["chunks"]), st.get("window", 0)))
-    queue.xor_stripes(descs, sources)
-    queue.sync()
-    return [dev.get(p, n) for p, n in outs]
 
 
 # --------------------------------------------------------------------------
@@ -147,7 +97,7 @@ def test_uniform_vs_oracle(oracle, dev, queue, nsrc, chunk):
     rng = np.random.default_rng(nsrc * 7 + chunk)
     data = rng.integers(0, 256, size=nstripes * nsrc * chunk, dtype=np.uint8)
     src = dev.put(data)
-    dst = dev.alloc(nstripes * chunk)
+    dst = dev.alloc(nstripes * chunk, fill=FILL)
     queue.xor_uniform(dst, src, nstripes, nsrc, chunk)
     out = dev.get(dst, nstripes * chunk)
     for s in range(nstripes):
@@ -162,13 +112,14 @@ def test_strided_layout(oracle, dev, queue):
     data = rng.integers(0, 256, size=nsrc * nstripes * chunk, dtype=np.uint8)  # [k][s][chunk]
     src = dev.put(data)
     pitch = chunk + 4096
-    dst = dev.alloc(nstripes * pitch)
+    dst = dev.alloc(nstripes * pitch, fill=FILL)
     queue.xor_strided(dst, pitch, src, chunk, nstripes * chunk, nstripes, nsrc, chunk)
     out = dev.get(dst, nstripes * pitch)
     d = data.reshape(nsrc, nstripes, chunk)
     for s in range(nstripes):
         ref = np.bitwise_xor.reduce(d[:, s, :], axis=0)
         assert np.array_equal(out[s * pitch:s * pitch + chunk], ref)
+        assert (out[s * pitch + chunk:(s + 1) * pitch] == FILL).all(), s  # the pitch gap stays as it was
 
 
 @pytest.mark.parametrize("bpc,vecs", [(1, 1), (2, 4), (4, 2), (8, 1), (16, 4), (1, 8), (3, 8)])
@@ -293,7 +244,7 @@ def test_work_queue_back_to_back_and_two_queues(oracle, engine, dev, queue):
         for i in range(24):
             n, chunk, ns = int(rng.integers(1, 10)), 16 * int(rng.integers(1, 40000)), int(rng.integers(1, 6))
             data = rng.integers(0, 256, size=ns * n * chunk, dtype=np.uint8)
-            src, dst = dev.put(data), dev.alloc(ns * chunk)
+            src, dst = dev.put(data), dev.alloc(ns * chunk, fill=FILL)
             queue.sync()  # the upload ran on `queue`; q2's kernel must see it
             q = queue if i % 3 else q2
             if i == 10:
@@ -602,12 +553,12 @@ def test_kernel_forms_agree(oracle, engine, dev, queue, knob, value, args_max):
         for chunk in (512 * KiB, 512 * KiB + 4096 + 16):
             data = rng.integers(0, 256, size=nstripes * nsrc * chunk, dtype=np.uint8)
             src = dev.put(data)
-            dst = dev.alloc(nstripes * chunk)
+            dst = dev.alloc(nstripes * chunk, fill=FILL)
             queue.xor_uniform(dst, src, nstripes, nsrc, chunk)
             ref = np.bitwise_xor.reduce(data.reshape(nstripes, nsrc, chunk), axis=1).reshape(-1)
             assert np.array_equal(dev.get(dst, nstripes * chunk), ref), chunk
             # pointer-table form (uniform descriptor batch)
-            dst2 = dev.alloc(nstripes * chunk)
+            dst2 = dev.alloc(nstripes * chunk, fill=FILL)
             queue.xor_stripes([(dst2 + s * chunk, chunk, s * nsrc, nsrc, 0) for s in range(nstripes)],
                               [(src + (s * nsrc + k) * chunk, chunk) for s in range(nstripes) for k in range(nsrc)])
             assert np.array_equal(dev.get(dst2, nstripes * chunk), ref), chunk
@@ -740,6 +691,80 @@ def test_empty_and_degenerate_stripes(oracle, dev, queue):
     assert not outs[4].any()
 
 
+@pytest.mark.parametrize("vecs", [1, 8, 16])
+def test_zero_region_past_the_longest_source(oracle, engine, dev, queue, vecs, desc_path):
+    """Outputs longer than every source: the bytes past the longest source are
+    zero padding only, in tiles no source reaches (whole subtiles of T = 256 *
+    vecs * 16 bytes, and the byte tail of the last).  out_len exceeds the
+    longest source by 1, 15, 16, T - 1, T and 3T + 5 at widths 1, 8 and 12
+    (wide tiles), with misaligned sources and outputs; a stripe whose sources
+    all have length 0 at valid addresses; a window-replay stripe (expected: the
+    reference's parity body, then zeros).  The output area holds 0xA5 before
+    the fold (gpu_stripes), so a store that is skipped leaves a wrong byte."""
+    T = 256 * vecs * 16
+    rng = np.random.default_rng(4100 + vecs)
+    batches = []
+    for j, extra in enumerate((1, 15, 16, T - 1, T, 3 * T + 5)):
+        small, rest = [], []  # small: fits the argument form (<= 8 sources, no window)
+        for width in (1, 8, 12):
+            top = 2 * T + 21 + 16 * j
+            lens = [top] + [int(x) for x in rng.integers(0, top + 1, size=width - 1)]
+            if width > 2:
+                lens[2] = top - 1  # ends one byte short of the longest
+            chunks = [rng.integers(0, 256, size=L, dtype=np.uint8) for L in lens]
+            st = dict(chunks=chunks, out_len=top + extra, pads=[int(x) for x in rng.integers(0, 16, size=width)],
+                      dst_pad=int(rng.integers(1, 16)))
+            (small if width <= 8 else rest).append((st, oracle.xor_padded_np(chunks)))
+        # every source empty, at a valid address: the whole output is padding
+        empty = [np.zeros(0, np.uint8) for _ in range(3)]
+        small.append((dict(chunks=empty, out_len=extra, pads=[3, 0, 9], dst_pad=5), oracle.xor_padded_np(empty)))
+        # window replay (a window that is a subtile multiple, and one that is not)
+        W = T if j % 2 == 0 else T + 16
+        lens = [3 * W + 5, W, W - 1, 2 * W + 16, 17, 0]
+        chunks = [rng.integers(0, 256, size=L, dtype=np.uint8) for L in lens]
+        assert W % 16 == 0 and W < max(lens)
+        body = np.frombuffer(oracle.gen_parity_file(chunks, window=W)[8 * len(lens):], np.uint8)
+        rest.append((dict(chunks=chunks, out_len=max(lens) + extra, window=W,
+                          pads=[int(x) for x in rng.integers(0, 16, size=len(lens))], dst_pad=7), body))
+        batches += [small, rest]
+    engine.option("desc_vecs_per_thread", vecs)
+    try:
+        for b, batch in enumerate(batches):
+            outs = gpu_stripes(dev, queue, [st for st, _ in batch])
+            refs = []
+            for st, body in batch:
+                ref = np.zeros(st["out_len"], np.uint8)  # the expected bytes, zero-extended to out_len
+                ref[:len(body)] = body
+                refs.append(ref)
+            assert_stripes_equal(outs, refs, f"batch {b} ({desc_path}, T {T})")
+    finally:
+        engine.option("desc_vecs_per_thread", 0)
+
+
+@pytest.mark.parametrize("window", [4096, 4096 + 16], ids=["remapped-tiles", "general-tiles"])
+def test_window_replay_ends_with_the_longest_source(oracle, engine, dev, queue, window):
+    """The replayed stream is as long as the longest source (the reference's
+    parity body); an output that is longer holds zeros from there on, not
+    the shorter source's window replayed once more.  The narrowest shape: two
+    sources, the short one a whole window (replayed over every later window),
+    4 KiB subtiles; the stream ends inside a vector, one byte and more than a
+    window before the output does."""
+    W = window
+    rng = np.random.default_rng(W)
+    chunks = [rng.integers(1, 256, size=L, dtype=np.uint8) for L in (3 * W + 5, W)]
+    body = np.frombuffer(oracle.gen_parity_file(chunks, window=W)[16:], np.uint8)
+    stripes, refs = [], []
+    for extra in (1, 16, W + 3):
+        stripes.append(dict(chunks=chunks, out_len=body.size + extra, window=W, pads=[3, 9], dst_pad=1))
+        refs.append(np.concatenate([body, np.zeros(extra, np.uint8)]))
+    engine.option("desc_vecs_per_thread", 1)
+    try:
+        outs = gpu_stripes(dev, queue, stripes)
+    finally:
+        engine.option("desc_vecs_per_thread", 0)
+    assert_stripes_equal(outs, refs)
+
+
 def test_invalid_descriptors_rejected(bcp, dev, queue):
     with pytest.raises(bcp.BcpError):
         queue.xor_stripes([(dev.alloc(64), 64, 0, 3, 0)], [(dev.alloc(64), 64)])   # sources out of range
@@ -775,6 +800,127 @@ def test_fold_and_compare(dev, queue):
     assert np.array_equal(fold, ref)
     queue.compare(pa, pb, a.size, res)
     assert int(dev.get(res, 8).view("<u8")[0]) == 4
+
+
+# The checkers themselves (bench.py's verified_on_device and the full-size
+# test rest on them) at 4 GiB + 64 KiB + 5 bytes: the smallest size at which a
+# 32-bit byte or vector index, or a count kept per grid sweep, goes wrong; a
+# 5-byte tail after the last whole vector.  No host-side gigabytes: the data is
+# fill_synthetic's, the second buffer a device copy of the first.
+BIG_N = (1 << 32) + 64 * KiB + 5
+BIG_SEED = 99
+BIG_LAST_VEC = BIG_N // 16 * 16 - 16
+# planted single-byte differences (offset, mask); 2^32 and 2^32 + 1 share a 32-bit word
+BIG_FLIPS = [[(0, 0x01), (15, 0x80), (16, 0x5A)],
+             [((1 << 32) - 1, 0xFF), (1 << 32, 0x10), ((1 << 32) + 1, 0x03)],
+             [(BIG_LAST_VEC, 0x40), (BIG_LAST_VEC + 15, 0x02), (BIG_N - 1, 0xA5)]]
+
+
+@pytest.fixture(scope="module")
+def big_pair(engine, queue):
+    """(dev, a, b): a = fill_synthetic(BIG_N, BIG_SEED), b = a device copy of
+    it.  Tests that change either buffer put the bytes back."""
+    d = Dev(engine, queue)
+    try:
+        a, b = d.alloc(BIG_N), d.alloc(BIG_N)
+        queue.fill_synthetic(a, BIG_N, BIG_SEED)
+        queue.d2d(b, a, BIG_N)
+        queue.sync()
+        yield d, a, b
+    finally:
+        d.free()
+
+
+def _flip(dev, queue, ptr, off, mask):
+    """XOR one device byte with mask through 1-byte copies."""
+    byte = dev.get(ptr + off, 1)
+    byte ^= np.uint8(mask)
+    queue.h2d(ptr + off, byte)
+    queue.sync()
+
+
+def _count(dev, queue, a, b, n, flag):
+    queue.memset(flag, 0xFF, 16)  # a stale count must not survive
+    queue.compare(a, b, n, flag)
+    return int(dev.get(flag, 8).view("<u8")[0])
+
+
+def test_compare_counts_every_byte_past_4gib(big_pair, queue):
+    dev, a, b = big_pair
+    flag = dev.alloc(16)
+    assert _count(dev, queue, a, b, BIG_N, flag) == 0
+    planted = 0
+    try:
+        for group in BIG_FLIPS:
+            for off, mask in group:
+                _flip(dev, queue, b, off, mask)
+            planted += len(group)
+            assert _count(dev, queue, a, b, BIG_N, flag) == planted, group
+            assert _count(dev, queue, b, a, BIG_N, flag) == planted, group
+        # a range that ends before the tail's difference, and the tail alone
+        assert _count(dev, queue, a, b, BIG_N - 1, flag) == planted - 1
+        assert _count(dev, queue, a + BIG_LAST_VEC + 16, b + BIG_LAST_VEC + 16, 5, flag) == 1
+    finally:
+        queue.d2d(b, a, BIG_N)
+        queue.sync()
+    assert _count(dev, queue, a, b, BIG_N, flag) == 0
+
+
+def _fold(dev, queue, ptr, n, res):
+    queue.memset(res, 0xFF, 16)  # xor_fold sets the result; it must not accumulate into what was there
+    queue.xor_fold(ptr, n, res)
+    return dev.get(res, 16).copy()
+
+
+def test_xor_fold_sees_every_byte_past_4gib(big_pair, queue):
+    """A flip of byte p by mask m changes fold byte p mod 16 by exactly m and
+    nothing else, wherever p lies; the fold of the whole is the XOR of the
+    folds of its two halves cut at 2^32."""
+    dev, a, b = big_pair
+    res = dev.alloc(16)
+    base = _fold(dev, queue, a, BIG_N, res)
+    assert base.any()
+    assert np.array_equal(_fold(dev, queue, a, BIG_N, res), base)  # a second fold into the same result
+    halves = _fold(dev, queue, a, 1 << 32, res) ^ _fold(dev, queue, a + (1 << 32), BIG_N - (1 << 32), res)
+    assert np.array_equal(halves, base)
+    for off, mask in [f for group in BIG_FLIPS for f in group]:
+        _flip(dev, queue, a, off, mask)
+        try:
+            got = _fold(dev, queue, a, BIG_N, res)
+        finally:
+            _flip(dev, queue, a, off, mask)
+        want = base.copy()
+        want[off % 16] ^= mask
+        assert np.array_equal(got, want), (off, mask)
+    assert np.array_equal(_fold(dev, queue, a, BIG_N, res), base)
+
+
+@pytest.mark.parametrize("n", [1, 15, 16, 17, 31])
+def test_xor_fold_small_sizes(dev, queue, n):
+    data = np.random.default_rng(n).integers(1, 256, size=n, dtype=np.uint8)
+    res = dev.alloc(16)
+    ref = np.zeros(16, np.uint8)
+    for i in range(n):
+        ref[i % 16] ^= data[i]
+    assert np.array_equal(_fold(dev, queue, dev.put(data), n, res), ref)
+
+
+def test_fill_synthetic_windows_past_4gib(oracle, big_pair, queue):
+    """64-byte windows of one fill of more than 4 GiB, around offset 2^32 and
+    at its end, against the oracle's stream; the same with a byte offset that
+    is not a multiple of 8 (the per-byte form) and lies above 2^33."""
+    dev, a, b = big_pair
+    wins = [(1 << 32) - 64, (1 << 32) - 32, 1 << 32, BIG_LAST_VEC - 48, BIG_N - 64]
+    for off in [0] + wins:
+        assert np.array_equal(dev.get(a + off, 64), oracle.synthetic(64, BIG_SEED, off)), off
+    boff = (1 << 33) + 3
+    try:
+        queue.fill_synthetic(b, BIG_N, BIG_SEED + 1, boff)
+        for off in [0] + wins:
+            assert np.array_equal(dev.get(b + off, 64), oracle.synthetic(64, BIG_SEED + 1, boff + off)), off
+    finally:
+        queue.d2d(b, a, BIG_N)
+        queue.sync()
 
 
 # --------------------------------------------------------------------------
@@ -878,11 +1024,11 @@ def test_narrow_stripes_multi_tile_grabs(engine, dev, queue, nsrc, vecs):
         for nstripes, chunk in ((37, 512 * KiB), (5, 3 * 32 * KiB + 48), (1, 16)):
             data = rng.integers(0, 256, size=nstripes * nsrc * chunk, dtype=np.uint8)
             src = dev.put(data)
-            dst = dev.alloc(nstripes * chunk)
+            dst = dev.alloc(nstripes * chunk, fill=FILL)
             queue.xor_uniform(dst, src, nstripes, nsrc, chunk)
             ref = np.bitwise_xor.reduce(data.reshape(nstripes, nsrc, chunk), axis=1).reshape(-1)
             assert np.array_equal(dev.get(dst, nstripes * chunk), ref), (nstripes, chunk)
-            dst2 = dev.alloc(nstripes * chunk)
+            dst2 = dev.alloc(nstripes * chunk, fill=FILL)
             queue.xor_stripes([(dst2 + s * chunk, chunk, s * nsrc, nsrc, 0) for s in range(nstripes)],
                               [(src + (s * nsrc + k) * chunk, chunk) for s in range(nstripes) for k in range(nsrc)])
             assert np.array_equal(dev.get(dst2, nstripes * chunk), ref), (nstripes, chunk)
@@ -898,7 +1044,7 @@ def test_budget_widths_default_tuning(engine, dev, queue, nsrc):
     for nstripes, chunk in ((300, 512 * KiB), (7, 5 * 16 * KiB + 32)):
         data = rng.integers(0, 256, size=nstripes * nsrc * chunk, dtype=np.uint8)
         src = dev.put(data)
-        dst = dev.alloc(nstripes * chunk)
+        dst = dev.alloc(nstripes * chunk, fill=FILL)
         queue.xor_uniform(dst, src, nstripes, nsrc, chunk)
         queue.sync()
         if nstripes == 300:
