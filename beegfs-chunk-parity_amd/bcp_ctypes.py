@@ -32,6 +32,14 @@ class Stripe(ctypes.Structure):
                 ("nsrc", ctypes.c_uint32), ("window", ctypes.c_uint64)]
 
 
+class CheckResult(ctypes.Structure):
+    """bcp_check_result: one record per stripe of a check batch."""
+    _fields_ = [("first_bad", ctypes.c_uint64), ("bad_bytes", ctypes.c_uint64)]
+
+
+CHECK_CLEAN = (2 ** 64 - 1, 0)  # (first_bad, bad_bytes) of a stripe whose dst equals the fold
+
+
 class FileInfo(ctypes.Structure):
     _fields_ = [("timestamp", ctypes.c_int64), ("locations", ctypes.c_uint64)]
 
@@ -50,6 +58,22 @@ class PipelineTiming(ctypes.Structure):
                 ("submit", ctypes.c_double), ("drain", ctypes.c_double), ("batches", ctypes.c_uint32),
                 ("read_jobs", ctypes.c_uint32), ("read_mode", ctypes.c_int),
                 ("direct_bytes", ctypes.c_uint64), ("direct_fallbacks", ctypes.c_uint32)]
+
+
+class VerifyItem(ctypes.Structure):
+    """bcp_verify_item: the scrub's verdict for one work item."""
+    _fields_ = [("status", ctypes.c_uint32), ("reserved", ctypes.c_uint32), ("first_bad", ctypes.c_uint64),
+                ("bad_bytes", ctypes.c_uint64)]
+
+
+class VerifyStats(ctypes.Structure):
+    _fields_ = [("seconds", ctypes.c_double), ("items", ctypes.c_uint64), ("ok", ctypes.c_uint64),
+                ("stale", ctypes.c_uint64), ("no_parity", ctypes.c_uint64), ("size", ctypes.c_uint64),
+                ("mismatch", ctypes.c_uint64), ("skipped", ctypes.c_uint64), ("refused", ctypes.c_uint64),
+                ("bytes_read", ctypes.c_uint64), ("errors", ctypes.c_int)]
+
+
+VERIFY_OK, VERIFY_STALE, VERIFY_NO_PARITY, VERIFY_SIZE, VERIFY_MISMATCH, VERIFY_SKIPPED = range(6)
 
 
 class PipelineOpts(ctypes.Structure):
@@ -115,6 +139,8 @@ _SIGS = {
                                ctypes.c_uint32, ctypes.c_uint64], ctypes.c_int),
     "bcp_xor_stripes_async": ([_V, ctypes.POINTER(Stripe), ctypes.c_uint32, ctypes.POINTER(Source), ctypes.c_uint32],
                               ctypes.c_int),
+    "bcp_check_stripes_async": ([_V, ctypes.POINTER(Stripe), ctypes.c_uint32, ctypes.POINTER(Source), ctypes.c_uint32,
+                                 _V], ctypes.c_int),
     "bcp_xor_parity": ([_V, ctypes.c_size_t, _V, ctypes.c_int], ctypes.c_int),
     "bcp_ring_create": ([_V, ctypes.c_int, ctypes.c_int, ctypes.POINTER(_V)], ctypes.c_int),
     "bcp_ring_submit": ([_V, ctypes.POINTER(Stripe), ctypes.POINTER(Source), ctypes.POINTER(ctypes.c_uint64)],
@@ -178,6 +204,9 @@ _SIGS = {
     "bcp_pipeline_last_timing": ([_V, ctypes.POINTER(PipelineTiming)], ctypes.c_int),
     "bcp_pipeline_rebuild": ([_V, ctypes.c_char_p, ctypes.c_int, ctypes.c_int, ctypes.POINTER(WorkItem),
                               ctypes.c_size_t, ctypes.c_char_p, _V, ctypes.POINTER(RunStats)], ctypes.c_int),
+    "bcp_pipeline_verify": ([_V, ctypes.c_char_p, ctypes.c_int, ctypes.POINTER(WorkItem), ctypes.c_size_t,
+                             ctypes.POINTER(VerifyItem), ctypes.c_char_p, _V, ctypes.POINTER(VerifyStats)],
+                            ctypes.c_int),
     "bcp_lb_init": ([ctypes.c_int], ctypes.c_int),
     "bcp_eventset_create": ([ctypes.POINTER(_V)], ctypes.c_int),
     "bcp_eventset_destroy": ([_V], None),
@@ -393,6 +422,13 @@ class Queue:
         st = (Stripe * max(len(stripes), 1))(*[Stripe(*s) for s in stripes])
         so = (Source * max(len(sources), 1))(*[Source(*s) for s in sources])
         call("bcp_xor_stripes_async", self.h, st, len(stripes), so, len(sources))
+
+    def check_stripes(self, stripes, sources, results_ptr: int):
+        """As xor_stripes, but every stripe's dst is compared with the fold instead of written;
+        results_ptr: device memory for len(stripes) CheckResult records."""
+        st = (Stripe * max(len(stripes), 1))(*[Stripe(*s) for s in stripes])
+        so = (Source * max(len(sources), 1))(*[Source(*s) for s in sources])
+        call("bcp_check_stripes_async", self.h, st, len(stripes), so, len(sources), _V(results_ptr))
 
     def fill_synthetic(self, dptr: int, nbytes: int, seed: int, byte_offset: int = 0):
         call("bcp_dev_fill_synthetic_async", self.h, _V(dptr), nbytes, seed, byte_offset)
@@ -743,6 +779,16 @@ class Pipeline:
              corrupt_list.encode() if corrupt_list else None, log, ctypes.byref(st))
         del keep
         return st
+
+    def verify(self, store_root: str, ntargets: int, items, bad_list: str | None = None, log=None):
+        """bcp_pipeline_verify (the scrub): (VerifyStats, [VerifyItem]), one verdict per item."""
+        arr, keep = _items(items)
+        st = VerifyStats()
+        res = (VerifyItem * max(len(items), 1))()
+        call("bcp_pipeline_verify", self.h, store_root.encode(), ntargets, arr, len(items), res,
+             bad_list.encode() if bad_list else None, log, ctypes.byref(st))
+        del keep
+        return st, list(res[:len(items)])
 
     def round(self, store_root: str, ntargets: int, events: "EventSet", cum_weight=None, log=None):
         """bcp_gen_round_pipeline: plan from events + DB, run batched, update the DB."""

@@ -42,7 +42,7 @@ struct bcp_engine {
   pthread_mutex_t lock = PTHREAD_MUTEX_INITIALIZER;
   std::atomic<int> last_stream_vecs{0};  // U of the latest xor_stream launch (tools)
   std::atomic<int> last_desc_vecs{0};    // U of the latest descriptor-kernel launch (tools)
-  std::atomic<int> last_desc_form{0};    // 1 xor_desc (desc_tiles), 2 xor_desc_args
+  std::atomic<int> last_desc_form{0};    // 1 xor_desc (desc_tiles), 2 xor_desc_args, 3 check_desc
 };
 
 namespace {
@@ -955,9 +955,13 @@ static int submit_desc_args(bcp_queue *q, const bcp_stripe *stripes, uint32_t ns
   return queue_launched(q, le, acc + (uint64_t)grid);
 }
 
-// Submit a descriptor batch (host arrays) on q.
+// Submit a descriptor batch (host arrays) on q: the fold into every stripe's
+// dst, or with `check` (nstripes device records) the comparison of the fold
+// with what is at dst (bcp_check_stripes_async).  A check batch always takes
+// the staged form (desc_tiles records + tile queue): its kernel is the check
+// variant of xor_desc, and the records are initialised on the queue first.
 static int submit_desc(bcp_queue *q, const bcp_stripe *stripes, uint32_t nstripes, const bcp_source *sources,
-                       uint32_t nsources) {
+                       uint32_t nsources, bcp_check_result *check = nullptr) {
   bcp_engine *e = q->eng;
   // Validate, count 32 KiB tiles (the tile size is chosen from them).
   uint64_t tiles8 = 0;
@@ -975,11 +979,16 @@ static int submit_desc(bcp_queue *q, const bcp_stripe *stripes, uint32_t nstripe
     }
     tiles8 += (s.out_len + desc_tile_bytes(8) - 1) / desc_tile_bytes(8);
   }
-  if (tiles8 == 0) return 0;
   if (tiles8 > 0xFFFFFFF0ull / 4) return -EINVAL;
+  if (check) {
+    if (q->broken) return -EIO;
+    (void)hipGetLastError();
+    HIP_RC(launch_check_init(q->stream, check, nstripes));
+  }
+  if (tiles8 == 0) return 0;
   const int vecs = desc_vecs_for(e, tiles8);
   const uint32_t tile_bytes = desc_tile_bytes(vecs);
-  if (uniform_batch(stripes, nstripes, sources)) {
+  if (!check && uniform_batch(stripes, nstripes, sources)) {
     const uint64_t len = stripes[0].out_len;
     const int sv = stream_vecs(e, len, nstripes, stripes[0].nsrc);
     const uint32_t tps = stream_tiles_per_stripe(len, sv);
@@ -1021,7 +1030,7 @@ static int submit_desc(bcp_queue *q, const bcp_stripe *stripes, uint32_t nstripe
     slot->used = true;
     return 0;
   }
-  {
+  if (!check) {
     // the argument form is instantiated up to U = 8 (its batches are small)
     const int rc = submit_desc_args(q, stripes, nstripes, sources, vecs > 8 ? 8 : vecs);
     if (rc <= 0) return rc;
@@ -1143,10 +1152,11 @@ static int submit_desc(bcp_queue *q, const bcp_stripe *stripes, uint32_t nstripe
   } else {
     HIP_RC(launch_desc_tiles(q->stream, b));
   }
-  const hipError_t le = launch_xor_desc(q->stream, grid, vecs, b);
+  const hipError_t le =
+      check ? launch_check_desc(q->stream, grid, vecs, b, check) : launch_xor_desc(q->stream, grid, vecs, b);
   if (le == hipSuccess) {
     e->last_desc_vecs.store(vecs, std::memory_order_relaxed);
-    e->last_desc_form.store(1, std::memory_order_relaxed);
+    e->last_desc_form.store(check ? 3 : 1, std::memory_order_relaxed);
   }
   if ((rc = queue_launched(q, le, (uint64_t)acc + (uint64_t)grid))) return rc;
   HIP_RC(hipEventRecord(slot->done, q->stream));
@@ -1176,6 +1186,15 @@ extern "C" int bcp_xor_stripes_async(bcp_queue *q, const bcp_stripe *stripes, ui
   int rc = set_device(q->eng);
   if (rc) return rc;
   return submit_desc(q, stripes, nstripes, sources, nsources);
+}
+
+extern "C" int bcp_check_stripes_async(bcp_queue *q, const bcp_stripe *stripes, uint32_t nstripes,
+                                       const bcp_source *sources, uint32_t nsources, bcp_check_result *results_dev) {
+  if (!q || (nstripes && !stripes) || (nsources && !sources) || (nstripes && !results_dev)) return -EINVAL;
+  if (!nstripes) return 0;
+  int rc = set_device(q->eng);
+  if (rc) return rc;
+  return submit_desc(q, stripes, nstripes, sources, nsources, results_dev);
 }
 
 extern "C" int bcp_xor_strided_async(bcp_queue *q, void *dst, uint64_t dst_stride, const void *src,

@@ -284,6 +284,11 @@ uint32_t stream_tiles_per_stripe(uint64_t chunk_bytes, int vecs);
 // launch_xor_stream.
 hipError_t launch_desc_tiles(hipStream_t st, const DescBatch &b);
 hipError_t launch_xor_desc(hipStream_t st, int grid, int vecs, const DescBatch &b);
+// Check form of launch_xor_desc (bcp_check_stripes_async): the same tiles and
+// work-queue accounting; every stripe's dst is read and compared, res[s] gets
+// the verdict.  launch_check_init sets n records to {UINT64_MAX, 0}.
+hipError_t launch_check_init(hipStream_t st, bcp_check_result *res, uint32_t n);
+hipError_t launch_check_desc(hipStream_t st, int grid, int vecs, const DescBatch &b, bcp_check_result *res);
 // Small batch in the arguments; same work-queue accounting (ntiles + grid).
 hipError_t launch_xor_desc_args(hipStream_t st, int grid, int vecs, const DescArgs &a);
 // Resident fold ring: 1 watcher workgroup + `workers`.

@@ -338,6 +338,111 @@ __device__ __forceinline__ void store_tail(glob<unsigned char> *d, uint64_t out_
 }
 
 // ---------------------------------------------------------------------------
+// Sinks of the descriptor fold.  StoreSink writes the fold to dst (xor_desc*).
+// CheckSink (check_desc*, bcp_check_stripes_async) compares it with the bytes
+// already at dst and stores nothing: every store site below becomes loads of
+// the expected bytes (16-byte non-temporal loads for whole vectors inside the
+// output, the straddle-safe load for the vector that crosses its end) XORed
+// into the fold, so a lane ends a tile with its difference vectors.  (Loading
+// them ahead of the sources instead, as the accumulators' initial value,
+// measured no faster on config-5 shapes and spilled at U = 16.)
+// Clean path: the lane ORs them, the wave takes one ballot; no store, no
+// atomic.  Mismatch path (ballot non-zero): each lane finds its smallest
+// differing byte offset and its differing-byte count, the wave reduces both
+// by shuffles, and one lane issues one fetch_min and one fetch_add (relaxed,
+// agent scope: the waves of a stripe run on every XCD) on the stripe's
+// record.  A plain tile's record does not name its stripe; the mismatch path
+// finds it by bisecting tile_start with the tile's index.
+// ---------------------------------------------------------------------------
+struct StoreSink {
+  static constexpr bool check = false;
+};
+struct CheckSink {
+  static constexpr bool check = true;
+  const bcp_stripe *stripes;   // the batch's tables, as in DescBatch
+  const uint32_t *tile_start;
+  uint32_t nstripes;
+  bcp_check_result *res;  // [nstripes]
+  uint32_t t;             // the tile's index in the batch (plain and grouped tiles)
+};
+
+__device__ __forceinline__ bool any4(v4u d) { return (d[0] | d[1] | d[2] | d[3]) != 0u; }
+
+// Difference of fold vector v (output offset off) with the expected bytes at
+// d + off: bytes at or past out_len are neither read nor compared.
+__device__ __forceinline__ v4u diff_tail(gbyte *d, uint64_t out_len, uint64_t off, v4u v) {
+  if (off + 16 <= out_len) return v ^ ld16(d + off);
+  if (off >= out_len) return zero4();
+  const uint32_t n = (uint32_t)(out_len - off);
+  v ^= load_straddle(d + off, n);
+#pragma unroll
+  for (uint32_t i = 0; i < 16; i++)
+    if (i >= n) v[i >> 2] &= ~(0xFFu << (8 * (i & 3)));
+  return v;
+}
+
+// Mismatch path, per lane: difference vector d at output offset off.
+__device__ __forceinline__ void lane_scan(v4u d, uint64_t off, uint64_t &first, uint32_t &n) {
+#pragma unroll
+  for (int c = 0; c < 4; c++) {
+    const unsigned int w = d[c];
+    if (w) {
+      n += ((w & 0xFFu) != 0) + ((w & 0xFF00u) != 0) + ((w & 0xFF0000u) != 0) + ((w & 0xFF000000u) != 0);
+      const uint64_t o = off + (uint32_t)c * 4u + ((uint32_t)__builtin_ctz(w) >> 3);
+      first = o < first ? o : first;
+    }
+  }
+}
+
+// Mismatch path, per wave (every lane of the wave calls it): reduce, then
+// lane 0's two atomics on the stripe's record.
+__device__ __forceinline__ void check_commit(bcp_check_result *rec, uint64_t first, uint32_t n) {
+  unsigned long long f = first, c = n;
+  for (int o = 32; o > 0; o >>= 1) {
+    const unsigned long long fo = __shfl_xor(f, o, 64);
+    f = fo < f ? fo : f;
+    c += __shfl_xor(c, o, 64);
+  }
+  if ((threadIdx.x & 63u) == 0 && c) {
+    __hip_atomic_fetch_min((unsigned long long *)&rec->first_bad, f, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    __hip_atomic_fetch_add((unsigned long long *)&rec->bad_bytes, c, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  }
+}
+
+// Mismatch path: the stripe of plain tile k.t (the largest s with
+// tile_start[s] <= t; stripes without tiles repeat their neighbour's start and
+// are never the largest) and the tile's offset inside it.
+__device__ __forceinline__ bcp_check_result *check_where(const CheckSink &k, uint64_t tile_dst, uint64_t &base) {
+  const_as<uint32_t> *ts = cst(k.tile_start);
+  uint32_t lo = 0, hi = k.nstripes;
+  while (hi - lo > 1) {
+    const uint32_t mid = lo + (hi - lo) / 2;
+    if (ts[mid] <= k.t) lo = mid;
+    else hi = mid;
+  }
+  base = tile_dst - cst(k.stripes)[lo].dst;
+  return k.res + lo;
+}
+
+// End of a tile in the check form: d[u] is the difference vector at offset
+// off0 + u * 1024 from tile_dst.  where(base) is evaluated on the mismatch
+// path only.
+template <int U, typename W>
+__device__ __forceinline__ void check_tile(const v4u (&d)[U], uint32_t off0, W where) {
+  v4u any = d[0];
+#pragma unroll
+  for (int u = 1; u < U; u++) any |= d[u];
+  if (__ballot(any4(any)) == 0) return;
+  uint64_t first = ~0ull;
+  uint32_t n = 0;
+#pragma unroll
+  for (int u = 0; u < U; u++) lane_scan(d[u], off0 + (uint32_t)u * 1024u, first, n);
+  uint64_t base = 0;
+  bcp_check_result *rec = where(base);
+  check_commit(rec, n ? base + first : ~0ull, n);
+}
+
+// ---------------------------------------------------------------------------
 // Descriptor kernel.  Tiles of tile_bytes output bytes are numbered across the
 // batch (tile_start prefix) and handed out by the same work queue as
 // xor_stream, one tile per grab.  A small setup kernel (desc_tiles) first writes one 16-byte
@@ -379,8 +484,8 @@ __device__ __forceinline__ void fold_cover(v4u (&acc)[U], P src, uint32_t lane_o
 // subtile instead, the loads of subtile j+1 cannot move above the stores of
 // subtile j -- the compiler cannot rule out aliasing -- and each subtile
 // drains the pipe: config-5 shapes 78 -> 70 %.)
-template <int C, int M, int U, typename RT>
-__device__ __forceinline__ void fold_group(const RT &r, uint32_t lane_off) {
+template <int C, int M, int U, typename RT, typename SINK = StoreSink>
+__device__ __forceinline__ void fold_group(const RT &r, uint32_t lane_off, const SINK &k = SINK{}) {
   constexpr uint32_t T = (uint32_t)kBlock * U * 16u;  // == b.tile_bytes
   v4u x[C][M][U];
 #pragma unroll
@@ -391,24 +496,50 @@ __device__ __forceinline__ void fold_group(const RT &r, uint32_t lane_off) {
 #pragma unroll
       for (int u = 0; u < U; u++) x[i][j][u] = __builtin_nontemporal_load(p + j * (T / 16) + u * 64);
   }
-  glob<v4u_u> *q = gp<v4u_u>(r.dst + lane_off);
+  if constexpr (SINK::check) {
+    // the expected bytes are one more covering source; the differences land in x[0]
+    const glob<v4u_u> *e = gp<const v4u_u>(r.dst + lane_off);
+    v4u any = zero4();
 #pragma unroll
-  for (int j = 0; j < M; j++)
+    for (int j = 0; j < M; j++)
 #pragma unroll
-    for (int u = 0; u < U; u++) {
-      v4u a = x[0][j][u];
+      for (int u = 0; u < U; u++) {
+        v4u a = __builtin_nontemporal_load(e + j * (T / 16) + u * 64);
 #pragma unroll
-      for (int i = 1; i < C; i++) a ^= x[i][j][u];
-      __builtin_nontemporal_store(a, q + j * (T / 16) + u * 64);
-    }
+        for (int i = 0; i < C; i++) a ^= x[i][j][u];
+        x[0][j][u] = a;
+        any |= a;
+      }
+    if (__ballot(any4(any)) == 0) return;
+    uint64_t first = ~0ull;
+    uint32_t n = 0;
+#pragma unroll
+    for (int j = 0; j < M; j++)
+#pragma unroll
+      for (int u = 0; u < U; u++) lane_scan(x[0][j][u], lane_off + (uint32_t)j * T + (uint32_t)u * 1024u, first, n);
+    uint64_t base = 0;
+    bcp_check_result *rec = check_where(k, r.dst, base);
+    check_commit(rec, n ? base + first : ~0ull, n);
+  } else {
+    glob<v4u_u> *q = gp<v4u_u>(r.dst + lane_off);
+#pragma unroll
+    for (int j = 0; j < M; j++)
+#pragma unroll
+      for (int u = 0; u < U; u++) {
+        v4u a = x[0][j][u];
+#pragma unroll
+        for (int i = 1; i < C; i++) a ^= x[i][j][u];
+        __builtin_nontemporal_store(a, q + j * (T / 16) + u * 64);
+      }
+  }
 }
 
 // General tile: window replay (quirk A3-q1; only when max_cs exceeds the
 // transfer window) or more than kTileSrcs sources reaching in.  Each output
 // vector on its own through the stripe/source tables; rare, so compact.
-template <int U>
+template <int U, typename SINK = StoreSink>
 __device__ __noinline__ void desc_tile_general(const DescBatch &b, uint32_t stripe, uint32_t tile,
-                                               uint32_t first_src) {
+                                               uint32_t first_src, SINK k = SINK{}) {
   const_as<bcp_stripe> *dp_ = cst(b.stripes) + stripe;
   const_as<bcp_source> *srcs = cst(b.sources) + first_src;
   const uint32_t nsrc = dp_->nsrc;
@@ -420,6 +551,8 @@ __device__ __noinline__ void desc_tile_general(const DescBatch &b, uint32_t stri
   glob<unsigned char> *dp = gp<unsigned char>(dp_->dst);
   const uint64_t lane_off = (uint64_t)tile * b.tile_bytes +
                             (uint64_t)((threadIdx.x >> 6) * (64u * U) + (threadIdx.x & 63u)) * 16u;
+  uint64_t first = ~0ull;  // check form: this lane's smallest differing offset and count
+  uint32_t nbad = 0;
 #pragma unroll 1
   for (int u = 0; u < U; u++) {
     const uint64_t off = lane_off + (uint64_t)u * 1024u;
@@ -438,8 +571,16 @@ __device__ __noinline__ void desc_tile_general(const DescBatch &b, uint32_t stri
           if (i >= keep) x[i >> 2] &= ~(0xFFu << (8 * (i & 3)));
       }
     }
-    store_tail(dp, out_len, off, x);
+    if constexpr (SINK::check) {
+      const v4u d = diff_tail(dp, out_len, off, x);
+      if (any4(d)) lane_scan(d, off, first, nbad);
+    } else {
+      store_tail(dp, out_len, off, x);
+    }
   }
+  // (the lanes left the loop at different u: the wave is whole again here)
+  if constexpr (SINK::check)
+    if (__ballot(nbad != 0)) check_commit(k.res + stripe, first, nbad);
 }
 
 // Source addresses of a staged run, offset to a tile (fold_cover's src[i]).
@@ -454,9 +595,9 @@ struct RunAt {
 // staged run (sorted longest first: [0, nfull) cover, [nfull, nany) end
 // inside): covering sources eight at a time through fold_cover, then the
 // partial ones, as in the plain path.
-template <int U, int PIPE>
+template <int U, int PIPE, typename SINK = StoreSink>
 __device__ __noinline__ void desc_tile_wide(const DescBatch &b, uint32_t stripe, uint32_t sub, uint32_t first_src,
-                                            uint32_t nfull, uint32_t nany) {
+                                            uint32_t nfull, uint32_t nany, SINK sink = SINK{}) {
   constexpr int WP = PIPE;  // the window also over the eight-at-a-time covering folds
   const_as<bcp_stripe> *dp_ = cst(b.stripes) + stripe;
   const_as<bcp_source> *srcs = cst(b.sources) + first_src;
@@ -486,7 +627,19 @@ __device__ __noinline__ void desc_tile_wide(const DescBatch &b, uint32_t stripe,
   }
   const uint64_t out_len = dp_->out_len;
   glob<unsigned char> *dp = gp<unsigned char>(dp_->dst + tile_off);
-  if (tile_off + b.tile_bytes <= out_len) {
+  if constexpr (SINK::check) {
+    if (tile_off + b.tile_bytes <= out_len) {
+#pragma unroll
+      for (int u = 0; u < U; u++) acc[u] ^= ld16(dp + lane_off + u * 1024u);
+    } else {
+#pragma unroll
+      for (int u = 0; u < U; u++) acc[u] = diff_tail(dp, out_len - tile_off, lane_off + u * 1024u, acc[u]);
+    }
+    check_tile<U>(acc, lane_off, [&](uint64_t &base) {
+      base = tile_off;
+      return sink.res + stripe;
+    });
+  } else if (tile_off + b.tile_bytes <= out_len) {
     glob<v4u_u> *q = (glob<v4u_u> *)(dp + lane_off);
 #pragma unroll
     for (int u = 0; u < U; u++) __builtin_nontemporal_store(acc[u], q + u * 64);
@@ -499,8 +652,8 @@ __device__ __noinline__ void desc_tile_wide(const DescBatch &b, uint32_t stripe,
 // One plain or grouped tile from its record r: any type with the DescTile
 // members (the device-written record read through the constant address
 // space, or the register view of xor_desc_args).  tile_bytes = kBlock*U*16.
-template <int U, int PIPE, typename RT>
-__device__ __forceinline__ void desc_plain(const RT &r, uint32_t tile_bytes) {
+template <int U, int PIPE, typename RT, typename SINK = StoreSink>
+__device__ __forceinline__ void desc_plain(const RT &r, uint32_t tile_bytes, const SINK &k = SINK{}) {
   const uint32_t meta = r.meta;
   // this lane's vector u = 0 inside the tile; vector u is at + u * 1024
   const uint32_t lane_off = ((threadIdx.x >> 6) * (64u * U) + (threadIdx.x & 63u)) * 16u;
@@ -511,7 +664,7 @@ __device__ __forceinline__ void desc_plain(const RT &r, uint32_t tile_bytes) {
 #define BCP_GROUP(c, mm) \
   case (c << 4 | mm):                                                 \
     if constexpr (c * mm <= group_rows(U)) {                           \
-      fold_group<c, mm, U>(r, lane_off);                               \
+      fold_group<c, mm, U>(r, lane_off, k);                            \
       return;                                                          \
     }                                                                  \
     break;
@@ -534,9 +687,16 @@ __device__ __forceinline__ void desc_plain(const RT &r, uint32_t tile_bytes) {
         case 2: fold_cover<2, U, FP>(acc, r.src, off); break;
         default: fold_cover<1, U, FP>(acc, r.src, off); break;
       }
-      glob<v4u_u> *q = gp<v4u_u>(r.dst + off);
+      if constexpr (SINK::check) {
+        const glob<v4u_u> *e = gp<const v4u_u>(r.dst + off);
 #pragma unroll
-      for (int u = 0; u < U; u++) __builtin_nontemporal_store(acc[u], q + u * 64);
+        for (int u = 0; u < U; u++) acc[u] ^= __builtin_nontemporal_load(e + u * 64);
+        check_tile<U>(acc, off, [&](uint64_t &base) { return check_where(k, r.dst, base); });
+      } else {
+        glob<v4u_u> *q = gp<v4u_u>(r.dst + off);
+#pragma unroll
+        for (int u = 0; u < U; u++) __builtin_nontemporal_store(acc[u], q + u * 64);
+      }
     }
     return;
   }
@@ -575,7 +735,16 @@ __device__ __forceinline__ void desc_plain(const RT &r, uint32_t tile_bytes) {
   }
   glob<unsigned char> *dp = gp<unsigned char>(r.dst);
   const uint32_t out_bytes = r.out_bytes;
-  if (out_bytes == tile_bytes) {
+  if constexpr (SINK::check) {
+    if (out_bytes == tile_bytes) {
+#pragma unroll
+      for (int u = 0; u < U; u++) acc[u] ^= ld16(dp + lane_off + u * 1024u);
+    } else {
+#pragma unroll
+      for (int u = 0; u < U; u++) acc[u] = diff_tail(dp, out_bytes, lane_off + u * 1024u, acc[u]);
+    }
+    check_tile<U>(acc, lane_off, [&](uint64_t &base) { return check_where(k, r.dst, base); });
+  } else if (out_bytes == tile_bytes) {
     glob<v4u_u> *q = (glob<v4u_u> *)(dp + lane_off);
 #pragma unroll
     for (int u = 0; u < U; u++) __builtin_nontemporal_store(acc[u], q + u * 64);
@@ -585,22 +754,24 @@ __device__ __forceinline__ void desc_plain(const RT &r, uint32_t tile_bytes) {
   }
 }
 
-template <int U, int PIPE>
-__device__ __forceinline__ void desc_tile(const DescBatch &b, uint32_t t) {
+template <int U, int PIPE, typename SINK>
+__device__ __forceinline__ void desc_tile(const DescBatch &b, uint32_t t, const SINK &k) {
   const_as<DescTile> &r = cst(b.tiles)[t];
   const uint32_t meta = r.meta;
   if (meta & kTileGeneral) {
+    // (the sink by value: the store form's is empty and takes no argument register)
     if (meta & kTileWide)
-      desc_tile_wide<U, PIPE>(b, r.src_bytes[0], r.src_bytes[1], r.src_bytes[2], meta & 0xFFu, (meta >> 8) & 0xFFu);
+      desc_tile_wide<U, PIPE>(b, r.src_bytes[0], r.src_bytes[1], r.src_bytes[2], meta & 0xFFu, (meta >> 8) & 0xFFu, k);
     else
-      desc_tile_general<U>(b, r.src_bytes[0], r.src_bytes[1], r.src_bytes[2]);
+      desc_tile_general<U>(b, r.src_bytes[0], r.src_bytes[1], r.src_bytes[2], k);
     return;
   }
-  desc_plain<U, PIPE>(r, b.tile_bytes);
+  desc_plain<U, PIPE>(r, b.tile_bytes, k);
 }
 
-template <int U, int PIPE>
-__device__ __forceinline__ void desc_body(const DescBatch &b) {
+// res == nullptr: the fold (StoreSink); else the check form.
+template <int U, int PIPE, bool CHECK = false>
+__device__ __forceinline__ void desc_body(const DescBatch &b, bcp_check_result *res = nullptr) {
   // Work queue, one tile per grab (two LDS slots as in stream_body).  A
   // grab-ahead form (the next tile taken and its record touched before the
   // current one is folded) measured no gain and is gone.
@@ -610,7 +781,8 @@ __device__ __forceinline__ void desc_body(const DescBatch &b) {
   uint32_t t = __builtin_amdgcn_readfirstlane(next[0]);
   int slot = 0;
   while (t < b.ntiles) {
-    desc_tile<U, PIPE>(b, t);
+    if constexpr (CHECK) desc_tile<U, PIPE>(b, t, CheckSink{b.stripes, b.tile_start, b.nstripes, res, t});
+    else desc_tile<U, PIPE>(b, t, StoreSink{});
     slot ^= 1;
     if (threadIdx.x == 0) next[slot] = queue_grab(b.ctr, b.base);
     __syncthreads();
@@ -627,6 +799,23 @@ __global__ __launch_bounds__(kBlock) void xor_desc(DescBatch b) {
 template <int U, int PIPE>
 __global__ __launch_bounds__(kBlock) void xor_desc_p(DescBatch b) {
   desc_body<U, PIPE>(b);
+}
+
+// The check form of both (bcp_check_stripes_async): same tiles, same queue,
+// the stripes' dst compared instead of written, one record per stripe in res
+// (initialised by check_init before the launch).
+template <int U>
+__global__ __launch_bounds__(kBlock) void check_desc(DescBatch b, bcp_check_result *res) {
+  desc_body<U, 0, true>(b, res);
+}
+template <int U, int PIPE>
+__global__ __launch_bounds__(kBlock) void check_desc_p(DescBatch b, bcp_check_result *res) {
+  desc_body<U, PIPE, true>(b, res);
+}
+
+__global__ __launch_bounds__(kBlock) void check_init(bcp_check_result *res, uint32_t n) {
+  const uint32_t i = blockIdx.x * kBlock + threadIdx.x;
+  if (i < n) res[i] = bcp_check_result{~0ull, 0ull};
 }
 
 // ---------------------------------------------------------------------------
@@ -1221,6 +1410,26 @@ hipError_t launch_xor_desc(hipStream_t st, int grid, int vecs, const DescBatch &
     case 1: hipLaunchKernelGGL((xor_desc<1>), dim3(grid), dim3(kBlock), 0, st, b); break;
     case 4: hipLaunchKernelGGL((xor_desc<4>), dim3(grid), dim3(kBlock), 0, st, b); break;
     default: hipLaunchKernelGGL((xor_desc<2>), dim3(grid), dim3(kBlock), 0, st, b); break;
+  }
+  return hipGetLastError();
+}
+
+hipError_t launch_check_init(hipStream_t st, bcp_check_result *res, uint32_t n) {
+  if (n == 0) return hipSuccess;
+  hipLaunchKernelGGL(check_init, dim3((n + kBlock - 1) / kBlock), dim3(kBlock), 0, st, res, n);
+  return hipGetLastError();
+}
+
+// The check variant of every instantiation launch_xor_desc dispatches.
+hipError_t launch_check_desc(hipStream_t st, int grid, int vecs, const DescBatch &b, bcp_check_result *res) {
+  if (b.ntiles == 0) return hipSuccess;
+  if ((uint32_t)grid > b.ntiles) grid = (int)b.ntiles;
+  switch (vecs) {
+    case 16: hipLaunchKernelGGL((check_desc_p<16, 5>), dim3(grid), dim3(kBlock), 0, st, b, res); break;
+    case 8: hipLaunchKernelGGL((check_desc_p<8, 5>), dim3(grid), dim3(kBlock), 0, st, b, res); break;
+    case 1: hipLaunchKernelGGL((check_desc<1>), dim3(grid), dim3(kBlock), 0, st, b, res); break;
+    case 4: hipLaunchKernelGGL((check_desc<4>), dim3(grid), dim3(kBlock), 0, st, b, res); break;
+    default: hipLaunchKernelGGL((check_desc<2>), dim3(grid), dim3(kBlock), 0, st, b, res); break;
   }
   return hipGetLastError();
 }

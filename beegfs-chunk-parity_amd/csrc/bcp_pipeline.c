@@ -31,6 +31,13 @@
  * u64 header), max_cs = max(header), and the lost chunk is written to the
  * victim's chunks directory truncated to header[index of the victim];
  * survivors newer than FileInfo.timestamp go to the corrupt list.
+ *
+ * Verify mode (bcp_pipeline_verify, the scrub) reads instead of writing: the
+ * sources of an item are its chunks (lengths from the parity header) and, last,
+ * the parity body; the device compares the fold of the chunks with the body
+ * where it lies in the input slab (bcp_check_stripes_async), 16 bytes per item
+ * come back in the output slab, and the completion stage turns them into
+ * verdicts.  No write jobs, nothing under the store changes.
  */
 #define _GNU_SOURCE
 #include <errno.h>
@@ -234,7 +241,26 @@ typedef struct {
     int batch;
     int prealloc;                        /* posix_fallocate the output first (not where the
                                             output target's directory is tmpfs: do_write) */
+    int verify;                          /* 1: verify task; sources 0..n-2 are the chunks, n-1 the
+                                            parity body (parity_src) */
+    size_t item;                         /* verify: index of the work item */
+    uint32_t status;                     /* verify: BCP_VERIFY_* or VERIFY_PENDING */
+    uint64_t first_bad, bad_bytes;       /* verify: the device's record */
 } task;
+
+#define VERIFY_PENDING 0xFFu             /* passed the stat phase: to be read and compared */
+
+/* Source k is read from the parity directory, after the u64 header. */
+static int src_is_parity(const task *t, int k)
+{
+    return (t->rebuild || t->verify) && k == t->parity_src;
+}
+
+/* Bytes a task takes in the output slab. */
+static uint64_t out_span(const task *t)
+{
+    return t->verify ? sizeof(bcp_check_result) : (t->out_len + 255u) / 256u * 256u;
+}
 
 typedef struct {
     job j;                               /* first: the pool's link */
@@ -273,6 +299,7 @@ typedef struct {
                              DIRECT pieces read through the page cache instead} */
     latch *done;
     int direct;
+    int *errors;          /* verify: counts sources that could not be read to their end (or NULL) */
 } read_arg;
 
 static uint64_t pieces_of(uint64_t size)
@@ -342,6 +369,46 @@ static void do_stat(job *p)
     task *t = a->t;
     char fn[4352];
     t->max_cs = 0;
+    if (t->verify) {
+        /* the parity header and size, every holder's chunk as it is now;
+         * precedence STALE, NO_PARITY, SIZE */
+        const int n = t->n - 1;
+        uint64_t header[MAX_STORAGE_TARGETS] = {0};
+        uint64_t fsize = 0;
+        int have = 0, stale = 0, resized = 0;
+        struct stat st;
+        chunk_file(fn, sizeof(fn), a->root, t->holders[n], "parity", t->path);
+        int fd = open(fn, O_RDONLY);
+        if (fd >= 0) {
+            if (fstat(fd, &st) == 0)
+                fsize = (uint64_t)st.st_size;
+            have = fsize >= (uint64_t)n * 8u && pread(fd, header, (size_t)n * 8u, 0) == (ssize_t)((size_t)n * 8u);
+            close(fd);
+        }
+        for (int k = 0; k < n; k++)
+            if (header[k] > t->max_cs)
+                t->max_cs = header[k];
+        for (int k = 0; k < n; k++) {
+            chunk_file(fn, sizeof(fn), a->root, t->holders[k], "chunks", t->path);
+            uint64_t cur = 0;
+            if (stat(fn, &st) == 0) {
+                cur = (uint64_t)st.st_size;
+                stale |= st.st_mtime > t->timestamp;
+            }
+            resized |= cur != header[k];
+            t->size[k] = header[k];
+            t->src_off[k] = 0;
+        }
+        t->src_off[n] = (uint64_t)n * 8u;
+        t->size[n] = t->max_cs;
+        t->out_len = t->max_cs;
+        t->status = stale                                                 ? BCP_VERIFY_STALE
+                    : !have || fsize != (uint64_t)n * 8u + t->max_cs ? BCP_VERIFY_NO_PARITY
+                    : resized                                             ? BCP_VERIFY_SIZE
+                                                                          : VERIFY_PENDING;
+        latch_down(a->done);
+        return;
+    }
     if (!t->rebuild) {
         for (int k = 0; k < t->n; k++) {
             chunk_file(fn, sizeof(fn), a->root, t->holders[k], "chunks", t->path);
@@ -412,8 +479,7 @@ static void do_read(job *p)
     int direct = 0, fell_back = 0;
     if (want) {
         char fn[4352];
-        const int is_parity = t->rebuild && a->k == t->parity_src;
-        chunk_file(fn, sizeof(fn), a->root, t->holders[a->k], is_parity ? "parity" : "chunks", t->path);
+        chunk_file(fn, sizeof(fn), a->root, t->holders[a->k], src_is_parity(t, a->k) ? "parity" : "chunks", t->path);
         int fd = -1;
         if (a->direct) {
             fd = open(fn, O_RDONLY | O_DIRECT);
@@ -472,6 +538,8 @@ static void do_read(job *p)
         data = (have < hi ? have : hi) > lo ? (have < hi ? have : hi) - lo : 0;
     }
     pthread_mutex_lock(&g_stat_lock);
+    if (a->errors && hi > lo && have < hi)
+        (*a->errors)++; /* shorter than at stat time, or unreadable: compared as zeros */
     a->bytes[0] += data;
     if (a->direct) {
         if (fell_back)
@@ -563,6 +631,26 @@ static void do_complete(job *p)
      * and touch neither `a` nor a pushed write job after handing it over. */
     const complete_arg a = *(complete_arg *)p;
     int rc = bcp_event_sync(a.S->ev_d);
+    if (a.first < a.last && a.tasks[a.first].verify) {
+        /* verify: the batch's records are its result; no writes */
+        if (rc) {
+            pthread_mutex_lock(&g_stat_lock);
+            *a.dev_rc = rc;
+            pthread_mutex_unlock(&g_stat_lock);
+        }
+        latch *done = &a.S->writes;
+        for (size_t i = a.first; i < a.last; i++) {
+            task *t = &a.tasks[i];
+            if (!rc) {
+                const bcp_check_result *r = (const bcp_check_result *)(a.S->h_out + t->out_off);
+                t->first_bad = r->first_bad;
+                t->bad_bytes = r->bad_bytes;
+                t->status = r->bad_bytes ? BCP_VERIFY_MISMATCH : BCP_VERIFY_OK;
+            }
+            latch_down(done);
+        }
+        return;
+    }
     if (rc) {
         pthread_mutex_lock(&g_stat_lock);
         *a.dev_rc = rc;
@@ -831,7 +919,7 @@ fail:
 }
 
 static int pipeline_exec(bcp_pipeline *pl, const char *store_root, task *tasks, size_t nt, int corrupt_fd,
-                         FILE *log, bcp_run_stats *stats, double t0);
+                         FILE *log, bcp_run_stats *stats, double t0, bcp_verify_item *vres);
 
 /* Bytes source k of t takes in the input slab: its data at 256-byte pitch
  * (COPY), or the whole file prefix up to the data's end at page pitch (DIRECT:
@@ -895,7 +983,7 @@ int bcp_pipeline_run(bcp_pipeline *pl, const char *store_root, int ntargets, con
             if (TEST_BIT(loc, k))
                 t->holders[t->n++] = k;
     }
-    rc = pipeline_exec(pl, store_root, tasks, nt, -1, log, stats, t0);
+    rc = pipeline_exec(pl, store_root, tasks, nt, -1, log, stats, t0, NULL);
     free(tasks);
     if (stats)
         stats->refused = bcpr_count_refused(items, nitems, -1);
@@ -949,7 +1037,7 @@ static int auto_read_mode(const char *root, const task *tasks, size_t nt, fs_kin
     int all_mem = 1;
     for (size_t i = 0; i < nt && all_mem; i++)
         for (int k = 0; k < tasks[i].n && all_mem; k++)
-            all_mem = dir_in_memory(fk, root, tasks[i].holders[k], tasks[i].rebuild && k == tasks[i].parity_src);
+            all_mem = dir_in_memory(fk, root, tasks[i].holders[k], src_is_parity(&tasks[i], k));
     if (all_mem)
         return BCP_READ_COPY;
     const uint64_t cap = (uint64_t)16 << 20;
@@ -963,8 +1051,7 @@ static int auto_read_mode(const char *root, const task *tasks, size_t nt, fs_kin
         for (int k = 0; k < t->n; k++) {
             if (!t->size[k])
                 continue;
-            const int is_parity = t->rebuild && k == t->parity_src;
-            chunk_file(fn, sizeof(fn), root, t->holders[k], is_parity ? "parity" : "chunks", t->path);
+            chunk_file(fn, sizeof(fn), root, t->holders[k], src_is_parity(t, k) ? "parity" : "chunks", t->path);
             const uint64_t len = t->src_off[k] + t->size[k] < cap ? t->src_off[k] + t->size[k] : cap;
             int fd = open(fn, O_RDONLY);
             if (fd < 0)
@@ -988,9 +1075,10 @@ static int auto_read_mode(const char *root, const task *tasks, size_t nt, fs_kin
 }
 
 /* Stat, batch and stream the tasks through the slots (both read paths).
- * Takes no ownership of tasks. */
+ * Takes no ownership of tasks.  vres: verify run (every task a verify task):
+ * the verdicts of the work items, written here for every task. */
 static int pipeline_exec(bcp_pipeline *pl, const char *store_root, task *tasks, size_t nt, int corrupt_fd,
-                         FILE *log, bcp_run_stats *stats, double t0)
+                         FILE *log, bcp_run_stats *stats, double t0, bcp_verify_item *vres)
 {
     fs_kinds fk;
     memset(&fk, -1, sizeof(fk));
@@ -1017,9 +1105,25 @@ static int pipeline_exec(bcp_pipeline *pl, const char *store_root, task *tasks, 
         latch_destroy(&l);
         free(args);
     }
+    const int verify = vres != NULL;
+    if (verify) {
+        /* only the items that passed the stat phase are read and compared:
+         * the others' verdicts stand, their tasks drop out (order kept) */
+        size_t w = 0;
+        for (size_t i = 0; i < nt; i++) {
+            if (tasks[i].status != VERIFY_PENDING) {
+                vres[tasks[i].item].status = tasks[i].status;
+                continue;
+            }
+            if (w != i)
+                tasks[w] = tasks[i];
+            w++;
+        }
+        nt = w;
+    }
     /* the reference reserves every output's space first (task_processing.c:186),
      * except where that output's directory is tmpfs / ramfs (do_write) */
-    for (size_t i = 0; i < nt; i++)
+    for (size_t i = 0; i < nt && !verify; i++)
         tasks[i].prealloc = !dir_in_memory(&fk, store_root, tasks[i].p, !tasks[i].rebuild);
 
     /* 2. plan batches: inputs at 256-byte pitch (DIRECT: page pitch), outputs
@@ -1033,8 +1137,8 @@ static int pipeline_exec(bcp_pipeline *pl, const char *store_root, task *tasks, 
             in += span_of(&tasks[i], k, dir);
         if (in > in_cap)
             in_cap = (size_t)in;
-        if (RUP(tasks[i].out_len) > out_cap)
-            out_cap = (size_t)RUP(tasks[i].out_len);
+        if (out_span(&tasks[i]) > out_cap)
+            out_cap = (size_t)out_span(&tasks[i]);
     }
     if ((rc = ensure_slots(pl, in_cap, out_cap))) {
         return rc;
@@ -1085,7 +1189,7 @@ static int pipeline_exec(bcp_pipeline *pl, const char *store_root, task *tasks, 
             uint64_t in = 0;
             for (int k = 0; k < t->n; k++)
                 in += span_of(t, k, dir);
-            if (i == 0 || in_used + in > limit || out_used + RUP(t->out_len) > out_cap) {
+            if (i == 0 || in_used + in > limit || out_used + out_span(t) > out_cap) {
                 nbatches++;
                 consumed += in_used;
                 in_used = out_used = 0;
@@ -1101,7 +1205,7 @@ static int pipeline_exec(bcp_pipeline *pl, const char *store_root, task *tasks, 
                 in_used += span_of(t, k, dir);
             }
             t->out_off = out_used;
-            out_used += RUP(t->out_len);
+            out_used += out_span(t);
         }
     }
     if (pl->desc_cap < nt) {
@@ -1186,7 +1290,7 @@ static int pipeline_exec(bcp_pipeline *pl, const char *store_root, task *tasks, 
                     for (uint64_t o = 0; o < e; o += PIECE) {
                         read_arg *a = &ra[rnext++];
                         *a = (read_arg){{0}, store_root, &tasks[i], k, o, e - o < PIECE ? e - o : PIECE, d + o, rd,
-                                        &B->S->reads, dir};
+                                        &B->S->reads, dir, verify ? &errors : NULL};
                         pool_push_hi(&pl->io, &a->j, do_read);
                     }
                 }
@@ -1207,18 +1311,23 @@ static int pipeline_exec(bcp_pipeline *pl, const char *store_root, task *tasks, 
         uint64_t out_used = 0;
         for (size_t i = first; i < last; i++) {
             task *t = &tasks[i];
-            st[ns] = (bcp_stripe){(uint64_t)S->d_out + t->out_off, t->out_len, nsrc, (uint32_t)t->n,
-                                  t->max_cs > WINDOW ? WINDOW : 0};
-            for (int k = 0; k < t->n; k++)
+            /* verify: dst is the parity body in the input slab (only read), the
+             * sources are the chunks before it */
+            const int nfold = verify ? t->n - 1 : t->n;
+            const uint64_t dst = verify ? (uint64_t)S->d_in + data_off(t, nfold, dir) : (uint64_t)S->d_out + t->out_off;
+            st[ns] = (bcp_stripe){dst, t->out_len, nsrc, (uint32_t)nfold, t->max_cs > WINDOW ? WINDOW : 0};
+            for (int k = 0; k < nfold; k++)
                 so[nsrc++] = (bcp_source){(uint64_t)S->d_in + data_off(t, k, dir), t->size[k]};
             ns++;
-            if (t->out_off + RUP(t->out_len) > out_used)
-                out_used = t->out_off + RUP(t->out_len);
+            if (t->out_off + out_span(t) > out_used)
+                out_used = t->out_off + out_span(t);
         }
         /* device: H2D (side queue) -> kernel -> D2H (side queue) */
         if ((in_used && (rc = bcp_h2d_async(L->qh, S->d_in, S->h_in, (size_t)in_used))) ||
             (rc = bcp_event_record(S->ev_h, L->qh)) || (rc = bcp_queue_wait_event(L->qk, S->ev_h)) ||
-            (rc = bcp_xor_stripes_async(L->qk, st, ns, so, nsrc)) || (rc = bcp_event_record(S->ev_k, L->qk)) ||
+            (rc = verify ? bcp_check_stripes_async(L->qk, st, ns, so, nsrc, (bcp_check_result *)S->d_out)
+                         : bcp_xor_stripes_async(L->qk, st, ns, so, nsrc)) ||
+            (rc = bcp_event_record(S->ev_k, L->qk)) ||
             (rc = bcp_queue_wait_event(L->qd, S->ev_k)) ||
             (rc = bcp_d2h_async(L->qd, S->h_out, S->d_out, (size_t)out_used)) ||
             (rc = bcp_event_record(S->ev_d, L->qd)))
@@ -1230,7 +1339,7 @@ static int pipeline_exec(bcp_pipeline *pl, const char *store_root, task *tasks, 
         complete_arg *ca = &cargs[b];
         *ca = (complete_arg){{0}, S, store_root, tasks, wa, first, last, &pl->io, log, &errors, &dev_rc};
         pool_push(&pl->completer, &ca->j, do_complete);
-        for (size_t i = first; i < last; i++)
+        for (size_t i = first; i < last && !verify; i++)
             bytes_written += (tasks[i].rebuild ? 0 : 8u * (uint64_t)tasks[i].n) + tasks[i].out_len;
         ntasks += last - first;
         tm.submit += now_s() - ts;
@@ -1273,6 +1382,19 @@ static int pipeline_exec(bcp_pipeline *pl, const char *store_root, task *tasks, 
     pl->last = tm;
     if (!rc && dev_rc)
         rc = dev_rc;
+    for (size_t i = 0; i < nt && verify; i++) {
+        bcp_verify_item *v = &vres[tasks[i].item];
+        if (tasks[i].status == VERIFY_PENDING) { /* its batch never came back */
+            v->status = BCP_VERIFY_SKIPPED;
+            errors++;
+            continue;
+        }
+        v->status = tasks[i].status;
+        if (tasks[i].status == BCP_VERIFY_MISMATCH) {
+            v->first_bad = tasks[i].first_bad;
+            v->bad_bytes = tasks[i].bad_bytes;
+        }
+    }
     if (stats) {
         memset(stats, 0, sizeof(*stats));
         stats->seconds = now_s() - t0;
@@ -1340,12 +1462,100 @@ int bcp_pipeline_rebuild(bcp_pipeline *pl, const char *store_root, int ntargets,
                 t->holders[t->n++] = k;
             }
     }
-    int rc = pipeline_exec(pl, store_root, tasks, nt, corrupt_fd, log, stats, t0);
+    int rc = pipeline_exec(pl, store_root, tasks, nt, corrupt_fd, log, stats, t0, NULL);
     free(tasks);
     if (stats)
         stats->refused = bcpr_count_refused(items, nitems, rebuild_target);
     if (corrupt_fd >= 0)
         close(corrupt_fd);
+    return rc;
+}
+
+int bcp_pipeline_verify(bcp_pipeline *pl, const char *store_root, int ntargets, const bcp_work_item *items,
+                        size_t nitems, bcp_verify_item *results, const char *bad_list_path, FILE *log,
+                        bcp_verify_stats *stats)
+{
+    if (!pl || !store_root || ntargets < 1 || ntargets > MAX_STORAGE_TARGETS || (nitems && !items))
+        return -EINVAL;
+    double t0 = now_s();
+    for (size_t i = 0; i < nitems; i++) {
+        uint64_t loc = items[i].fi.locations;
+        int P = GET_P(loc);
+        if ((uint64_t)P == NO_P)
+            continue;
+        if (!items[i].path || P >= ntargets || TEST_BIT(loc, P) || ((loc & L_MASK) >> ntargets))
+            return -EINVAL;
+    }
+    bcp_verify_item *res = results ? results : calloc(nitems ? nitems : 1, sizeof(*res));
+    task *tasks = calloc(nitems ? nitems : 1, sizeof(task));
+    int bad_fd = -1, rc = 0;
+    if (!res || !tasks) {
+        rc = -ENOMEM;
+        goto out;
+    }
+    if (bad_list_path) {
+        bad_fd = open(bad_list_path, O_WRONLY | O_CREAT | O_TRUNC | O_APPEND, S_IRUSR | S_IWUSR);
+        if (bad_fd < 0) {
+            rc = -errno;
+            goto out;
+        }
+    }
+    uint64_t refused = 0;
+    size_t nt = 0;
+    for (size_t i = 0; i < nitems; i++) {
+        const FileInfo *fi = &items[i].fi;
+        const int P = GET_P(fi->locations);
+        res[i] = (bcp_verify_item){BCP_VERIFY_SKIPPED, 0, UINT64_MAX, 0};
+        if ((uint64_t)P == NO_P || (fi->locations & L_MASK) == 0)
+            continue;
+        if (!bcpi_path_ok(items[i].path, (size_t)-1)) {
+            if (log)
+                fprintf(log, "bcp_pipeline: refusing '%s': not a path inside the store\n", items[i].path);
+            refused++;
+            continue;
+        }
+        task *t = &tasks[nt++];
+        t->path = items[i].path;
+        t->p = P;
+        t->verify = 1;
+        t->item = i;
+        t->timestamp = fi->timestamp;
+        for (int k = 0; k < MAX_STORAGE_TARGETS; k++)
+            if (TEST_BIT(fi->locations, k))
+                t->holders[t->n++] = k;
+        t->parity_src = t->n; /* the body: the last source, held by P */
+        t->holders[t->n++] = P;
+    }
+    bcp_run_stats rs = {0};
+    rc = pipeline_exec(pl, store_root, tasks, nt, -1, log, &rs, t0, res);
+    bcp_verify_stats vs = {0};
+    vs.items = nitems;
+    vs.refused = refused;
+    vs.bytes_read = rs.bytes_read;
+    vs.errors = rs.errors + (rc != 0);
+    for (size_t i = 0; i < nitems; i++) {
+        switch (res[i].status) {
+        case BCP_VERIFY_OK: vs.ok++; break;
+        case BCP_VERIFY_STALE: vs.stale++; break;
+        case BCP_VERIFY_NO_PARITY: vs.no_parity++; break;
+        case BCP_VERIFY_SIZE: vs.size++; break;
+        case BCP_VERIFY_MISMATCH: vs.mismatch++; break;
+        default: vs.skipped++; break;
+        }
+        /* the bad list after the run, in item order */
+        if (res[i].status == BCP_VERIFY_NO_PARITY || res[i].status == BCP_VERIFY_SIZE ||
+            res[i].status == BCP_VERIFY_MISMATCH)
+            push_corrupt(bad_fd, items[i].path);
+    }
+    vs.seconds = now_s() - t0;
+    if (stats)
+        *stats = vs;
+out:
+    if (bad_fd >= 0)
+        close(bad_fd);
+    free(tasks);
+    if (res != results)
+        free(res);
     return rc;
 }
 

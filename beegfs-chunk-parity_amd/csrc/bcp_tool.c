@@ -31,6 +31,15 @@
  *       beegfs-parity-rebuild + bp-parity-rebuild (rebuild/main.c), through
  *       the batched pipeline (default), the per-rank protocol (--protocol)
  *       or rank processes (--procs).
+ *   bcp parity-verify [--db DIR] [--bad FILE] [--read PATH] <store_root> <ntargets>
+ *       The scrub (no counterpart in the reference): for every item of the
+ *       database (default <root>/st0/db) the batched pipeline reads the chunks
+ *       and the parity body and compares them on the device
+ *       (bcp_pipeline_verify); nothing under the store is written.  One
+ *       summary line; --bad FILE lists the paths whose parity is missing,
+ *       has the wrong size or differs.  Exit 0 when nothing is NO_PARITY, SIZE
+ *       or MISMATCH, nothing was refused and no read or device error occurred
+ *       (stale items -- chunks modified since the last round -- are clean).
  *
  * Items whose path would leave the store (absolute, "..") are skipped and
  * counted as refused; a run with refused items exits 1.
@@ -56,6 +65,7 @@ static int usage(void)
           "                      [--lanes N] [--force] [--changelog DIR] <store_root> <ntargets>\n"
           "       bcp parity-rebuild [--pipeline|--protocol|--procs] [--fold MODE] [--read PATH] [--lanes N]\n"
           "                          [--db DIR] [--corrupt FILE] <store_root> <ntargets> <target>\n"
+          "       bcp parity-verify [--db DIR] [--bad FILE] [--read PATH] <store_root> <ntargets>\n"
           "       engine: --pipeline (default: batched pipeline on every GPU) | --protocol (per-rank\n"
           "               process_task, ranks as threads) | --procs (ranks as processes)\n"
           "       MODE (protocol P-role fold): pipelined (default) | batched\n"
@@ -383,6 +393,65 @@ static int cmd_rebuild(int argc, char **argv)
     return (st.errors || st.refused) ? 1 : 0;
 }
 
+static int cmd_verify(int argc, char **argv)
+{
+    const char *db = NULL, *bad = NULL;
+    int i = 0;
+    for (; i < argc && argv[i][0] == '-'; i++) {
+        if (!strcmp(argv[i], "--db") && i + 1 < argc)
+            db = argv[++i];
+        else if (!strcmp(argv[i], "--bad") && i + 1 < argc)
+            bad = argv[++i];
+        else if (!strcmp(argv[i], "--read") && i + 1 < argc) {
+            if ((g_read_mode = read_mode_arg(argv[++i])) < 0)
+                return usage();
+        } else
+            return usage();
+    }
+    if (argc - i != 2)
+        return usage();
+    const char *root = argv[i];
+    const int ntargets = atoi(argv[i + 1]);
+    if (ntargets < 1 || ntargets > MAX_STORAGE_TARGETS)
+        return usage();
+    char dp[4096];
+    if (!db) {
+        snprintf(dp, sizeof(dp), "%s/st0/db", root);
+        db = dp;
+    }
+    struct stat sb;
+    bcp_pdb *pdb = NULL;
+    bcp_work_item *items = NULL;
+    size_t n = 0;
+    bcp_verify_stats vs;
+    memset(&vs, 0, sizeof(vs));
+    int rc = stat(db, &sb) == 0 ? 0 : -errno;
+    if (!rc)
+        rc = bcp_pdb_open(db, DB_VERSION, &pdb);
+    if (!rc) {
+        rc = bcp_pdb_items(pdb, &items, &n);
+        bcp_pdb_close(pdb);
+    }
+    if (!rc) {
+        bcp_pipeline *pl = NULL;
+        rc = pipeline_on_all_gpus(&pl, 0);
+        if (!rc)
+            rc = bcp_pipeline_verify(pl, root, ntargets, items, n, NULL, bad, stderr, &vs);
+        if (pl)
+            bcp_pipeline_destroy(pl);
+    }
+    bcp_pdb_items_free(items);
+    if (rc)
+        return fail("parity-verify", rc);
+    printf("verified %llu items: %llu ok, %llu stale, %llu no parity, %llu wrong size, %llu mismatch, %llu skipped "
+           "(%llu refused), %d errors, %.3f s, %.1f MiB read\n",
+           (unsigned long long)vs.items, (unsigned long long)vs.ok, (unsigned long long)vs.stale,
+           (unsigned long long)vs.no_parity, (unsigned long long)vs.size, (unsigned long long)vs.mismatch,
+           (unsigned long long)vs.skipped, (unsigned long long)vs.refused, vs.errors, vs.seconds,
+           vs.bytes_read / 1048576.0);
+    return (vs.no_parity || vs.size || vs.mismatch || vs.refused || vs.errors) ? 1 : 0;
+}
+
 int main(int argc, char **argv)
 {
     if (argc < 2)
@@ -393,5 +462,7 @@ int main(int argc, char **argv)
         return cmd_gen(argc - 2, argv + 2);
     if (!strcmp(argv[1], "parity-rebuild"))
         return cmd_rebuild(argc - 2, argv + 2);
+    if (!strcmp(argv[1], "parity-verify"))
+        return cmd_verify(argc - 2, argv + 2);
     return usage();
 }

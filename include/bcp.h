@@ -44,7 +44,10 @@ extern "C" {
 #endif
 
 /* 4 (r06): the resident fold ring (bcp_ring_*) and the P role's fold
- * through it (bcp_task.h, bcp_task_set_fold_ring) added.
+ * through it (bcp_task.h, bcp_task_set_fold_ring) added.  Later additions
+ * under 4 (nothing existing changed): the parity scrub's
+ * bcp_check_stripes_async / bcp_check_result, and the "last_desc_form"
+ * value 3.
  * 3 (r05): the pipeline's MAP read mode (BCP_READ_MAP), its
  * bcp_pipeline_timing fields and bcp_host_register_dma_src removed.
  * 2 (r04): bcp_task.h's bcp_run_stats gained `refused`, bcp_pipeline_opts
@@ -166,6 +169,21 @@ int bcp_xor_stripes_async(bcp_queue *q, const bcp_stripe *stripes,
                           uint32_t nstripes, const bcp_source *sources,
                           uint32_t nsources);
 
+/* One record per stripe of a check batch (bcp_check_stripes_async). */
+typedef struct bcp_check_result {
+    uint64_t first_bad;   /* smallest j in [0, out_len) with fold[j] != dst[j]; UINT64_MAX if none */
+    uint64_t bad_bytes;   /* number of such j (bytes, not vectors) */
+} bcp_check_result;
+/* Compare instead of store: for every stripe, what bcp_xor_stripes_async would
+ * write to [dst, dst+out_len) against what is there.  dst is only read.
+ * results_dev: nstripes records in device memory (bcp_dev_alloc), fully
+ * written by this call's work for every stripe -- {UINT64_MAX, 0} for a clean
+ * one, also for out_len == 0 and for batches with no tile at all.  Both
+ * fields are exact.  Nothing is read outside [dst, dst+out_len). */
+int bcp_check_stripes_async(bcp_queue *q, const bcp_stripe *stripes,
+                            uint32_t nstripes, const bcp_source *sources,
+                            uint32_t nsources, bcp_check_result *results_dev);
+
 /* ---- resident fold ring ------------------------------------------------ */
 /* One kernel launch that stays on the device and folds stripes published
  * into a ring of descriptors in pinned host memory: no launch and no stream
@@ -271,7 +289,8 @@ int bcp_set_option(bcp_engine *eng, const char *key, int value);
 /* Current value of a named knob (same keys), or of the engine's latest
  * launch: "last_stream_vecs" (vecs_per_thread of the streaming kernel),
  * "last_desc_vecs" and "last_desc_form" (descriptor kernel: 1 = desc_tiles +
- * xor_desc, 2 = xor_desc_args). */
+ * xor_desc, 2 = xor_desc_args, 3 = desc_tiles + the check kernel of
+ * bcp_check_stripes_async). */
 int bcp_get_option(bcp_engine *eng, const char *key, int *value);
 /* Timer slots for bcp_queue_mark / bcp_queue_elapsed_ms. */
 #define BCP_TIMER_SLOTS 64

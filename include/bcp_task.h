@@ -646,6 +646,44 @@ int bcp_pipeline_last_timing(const bcp_pipeline *pl, bcp_pipeline_timing *out);
 int bcp_pipeline_rebuild(bcp_pipeline *pl, const char *store_root, int ntargets, int rebuild_target,
                          const bcp_work_item *items, size_t nitems, const char *corrupt_list_path, FILE *log,
                          bcp_run_stats *stats);
+/* Parity scrub (the reference has no counterpart): is every item's parity on
+ * disk still the XOR of its chunks on disk?  The same machinery as gen and
+ * rebuild -- stat jobs, 1 MiB read jobs into the pinned input slab, both read
+ * paths, slots, round-robin over devices -- but per item the n chunks (lengths
+ * from the parity header) and the parity body (file offset 8n) are read, the
+ * device compares the fold of the chunks with the body where it lies in the
+ * input slab (bcp_check_stripes_async) and only 16 bytes per item come back.
+ * Nothing under the store is created, modified or unlinked.
+ * Per item, in this precedence: */
+#define BCP_VERIFY_OK        0  /* body == fold of the chunks */
+#define BCP_VERIFY_STALE     1  /* a holder's chunk mtime > FileInfo.timestamp: expected in a delayed
+                                   scheme, not compared, not an error (the corrupt-list rule) */
+#define BCP_VERIFY_NO_PARITY 2  /* parity file missing, shorter than its header, or its size
+                                   != 8*n + max(header) */
+#define BCP_VERIFY_SIZE      3  /* a holder's chunk size now != its size in the header (missing = 0) */
+#define BCP_VERIFY_MISMATCH  4  /* compared on the device and different */
+#define BCP_VERIFY_SKIPPED   5  /* NO_P item, item without holders, or refused path */
+/* (SKIPPED, then STALE, NO_PARITY, SIZE; only items that pass all four are
+ * read and compared.) */
+typedef struct {
+    uint32_t status, reserved;
+    uint64_t first_bad, bad_bytes; /* MISMATCH: smallest differing offset of the body, differing bytes */
+} bcp_verify_item;
+typedef struct {
+    double seconds;
+    uint64_t items, ok, stale, no_parity, size, mismatch, skipped, refused;
+    uint64_t bytes_read;
+    int errors;            /* read / device errors: the verdicts of those items are not to be trusted */
+} bcp_verify_stats;
+/* results: nitems records, or NULL.  bad_list_path (or NULL) is created and
+ * truncated like the corrupt list and receives one path per line for every
+ * NO_PARITY, SIZE and MISMATCH item, in item order.  Items are validated as
+ * by bcp_pipeline_rebuild (-EINVAL for bad locations); refused paths are
+ * logged, counted in `refused` and reported SKIPPED.
+ * bcp_pipeline_last_timing works after a verify run.  (Added under ABI 4.) */
+int bcp_pipeline_verify(bcp_pipeline *pl, const char *store_root, int ntargets, const bcp_work_item *items,
+                        size_t nitems, bcp_verify_item *results, const char *bad_list_path, FILE *log,
+                        bcp_verify_stats *stats);
 /* bcp_gen_round with the batched pipeline as the engine; the replicas are
  * updated after the run, only when it finished without errors. */
 int bcp_gen_round_pipeline(bcp_pipeline *pl, const char *store_root, int ntargets, const bcp_eventset *events,
