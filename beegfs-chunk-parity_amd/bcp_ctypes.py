@@ -37,6 +37,21 @@ class CheckResult(ctypes.Structure):
     _fields_ = [("first_bad", ctypes.c_uint64), ("bad_bytes", ctypes.c_uint64)]
 
 
+class PqLost(ctypes.Structure):
+    """bcp_pq_lost: what bcp_pq_recover_stripes_async rebuilds of one stripe."""
+    _fields_ = [("p", ctypes.c_uint64), ("q", ctypes.c_uint64), ("x", ctypes.c_uint32), ("y", ctypes.c_uint32),
+                ("dst_x", ctypes.c_uint64), ("len_x", ctypes.c_uint64), ("dst_y", ctypes.c_uint64),
+                ("len_y", ctypes.c_uint64)]
+
+
+PQ_NONE = 0xFFFFFFFF  # PqLost.y: only x is lost
+
+
+class Rebuild2Stats(ctypes.Structure):
+    _fields_ = [("xor_items", ctypes.c_uint64), ("q_items", ctypes.c_uint64), ("pq_items", ctypes.c_uint64),
+                ("unrecoverable", ctypes.c_uint64)]
+
+
 CHECK_CLEAN = (2 ** 64 - 1, 0)  # (first_bad, bad_bytes) of a stripe whose dst equals the fold
 
 
@@ -141,6 +156,11 @@ _SIGS = {
                               ctypes.c_int),
     "bcp_check_stripes_async": ([_V, ctypes.POINTER(Stripe), ctypes.c_uint32, ctypes.POINTER(Source), ctypes.c_uint32,
                                  _V], ctypes.c_int),
+    "bcp_pq_stripes_async": ([_V, ctypes.POINTER(Stripe), ctypes.c_uint32, ctypes.POINTER(Source), ctypes.c_uint32,
+                              ctypes.POINTER(ctypes.c_uint64)], ctypes.c_int),
+    "bcp_pq_recover_stripes_async": ([_V, ctypes.POINTER(Stripe), ctypes.c_uint32, ctypes.POINTER(Source),
+                                      ctypes.c_uint32, ctypes.POINTER(PqLost)], ctypes.c_int),
+    "bcp_q_target": ([ctypes.c_uint64, ctypes.c_int], ctypes.c_int),
     "bcp_xor_parity": ([_V, ctypes.c_size_t, _V, ctypes.c_int], ctypes.c_int),
     "bcp_ring_create": ([_V, ctypes.c_int, ctypes.c_int, ctypes.POINTER(_V)], ctypes.c_int),
     "bcp_ring_submit": ([_V, ctypes.POINTER(Stripe), ctypes.POINTER(Source), ctypes.POINTER(ctypes.c_uint64)],
@@ -207,6 +227,12 @@ _SIGS = {
     "bcp_pipeline_verify": ([_V, ctypes.c_char_p, ctypes.c_int, ctypes.POINTER(WorkItem), ctypes.c_size_t,
                              ctypes.POINTER(VerifyItem), ctypes.c_char_p, _V, ctypes.POINTER(VerifyStats)],
                             ctypes.c_int),
+    "bcp_pipeline_set_q_parity": ([_V, ctypes.c_int], ctypes.c_int),
+    "bcp_pipeline_q_stats": ([_V, ctypes.POINTER(ctypes.c_uint64), ctypes.POINTER(ctypes.c_uint64),
+                              ctypes.POINTER(ctypes.c_uint64)], ctypes.c_int),
+    "bcp_pipeline_rebuild2": ([_V, ctypes.c_char_p, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.POINTER(WorkItem),
+                               ctypes.c_size_t, ctypes.c_char_p, ctypes.c_char_p, _V, ctypes.POINTER(RunStats),
+                               ctypes.POINTER(Rebuild2Stats)], ctypes.c_int),
     "bcp_lb_init": ([ctypes.c_int], ctypes.c_int),
     "bcp_eventset_create": ([ctypes.POINTER(_V)], ctypes.c_int),
     "bcp_eventset_destroy": ([_V], None),
@@ -284,6 +310,11 @@ def check(fn: str, rc: int) -> int:
 
 def call(fn: str, *args) -> int:
     return check(fn, getattr(lib(), fn)(*args))
+
+
+def q_target(locations: int, ntargets: int) -> int:
+    """bcp_q_target: the storage target of an item's Q file, or -1."""
+    return lib().bcp_q_target(locations, ntargets)
 
 
 def device_count() -> int:
@@ -429,6 +460,22 @@ class Queue:
         st = (Stripe * max(len(stripes), 1))(*[Stripe(*s) for s in stripes])
         so = (Source * max(len(sources), 1))(*[Source(*s) for s in sources])
         call("bcp_check_stripes_async", self.h, st, len(stripes), so, len(sources), _V(results_ptr))
+
+    def pq_stripes(self, stripes, sources, q_dst):
+        """P and Q of every stripe: stripes as in xor_stripes (dst = P body, 0: no P), q_dst: the
+        Q body of each stripe; source k of a stripe's run has coefficient g^k."""
+        st = (Stripe * max(len(stripes), 1))(*[Stripe(*s) for s in stripes])
+        so = (Source * max(len(sources), 1))(*[Source(*s) for s in sources])
+        qd = (ctypes.c_uint64 * max(len(q_dst), 1))(*q_dst)
+        call("bcp_pq_stripes_async", self.h, st, len(stripes), so, len(sources), qd)
+
+    def pq_recover(self, stripes, sources, lost):
+        """lost: one PqLost (or tuple of its fields: p, q, x, y, dst_x, len_x, dst_y, len_y) per
+        stripe; the stripes list the survivors in position order, lost positions with len 0."""
+        st = (Stripe * max(len(stripes), 1))(*[Stripe(*s) for s in stripes])
+        so = (Source * max(len(sources), 1))(*[Source(*s) for s in sources])
+        lo = (PqLost * max(len(lost), 1))(*[x if isinstance(x, PqLost) else PqLost(*x) for x in lost])
+        call("bcp_pq_recover_stripes_async", self.h, st, len(stripes), so, len(sources), lo)
 
     def fill_synthetic(self, dptr: int, nbytes: int, seed: int, byte_offset: int = 0):
         call("bcp_dev_fill_synthetic_async", self.h, _V(dptr), nbytes, seed, byte_offset)
@@ -789,6 +836,27 @@ class Pipeline:
              bad_list.encode() if bad_list else None, log, ctypes.byref(st))
         del keep
         return st, list(res[:len(items)])
+
+    def set_q_parity(self, on: bool):
+        """Runs also write Q files (<root>/st<q>/parityq/<path>) when on; off by default."""
+        call("bcp_pipeline_set_q_parity", self.h, int(bool(on)))
+
+    def q_stats(self) -> dict:
+        """Q files of the last run: written, and items left with P only (no Q target / windowed)."""
+        w, n, x = ctypes.c_uint64(0), ctypes.c_uint64(0), ctypes.c_uint64(0)
+        call("bcp_pipeline_q_stats", self.h, ctypes.byref(w), ctypes.byref(n), ctypes.byref(x))
+        return {"written": w.value, "no_target": n.value, "windowed": x.value}
+
+    def rebuild2(self, store_root: str, ntargets: int, target_a: int, target_b: int, items,
+                 corrupt_list: str | None = None, lost_list: str | None = None, log=None):
+        """bcp_pipeline_rebuild2: rebuild the chunks of two lost targets; (RunStats, Rebuild2Stats)."""
+        arr, keep = _items(items)
+        st, st2 = RunStats(), Rebuild2Stats()
+        call("bcp_pipeline_rebuild2", self.h, store_root.encode(), ntargets, target_a, target_b, arr, len(items),
+             corrupt_list.encode() if corrupt_list else None, lost_list.encode() if lost_list else None, log,
+             ctypes.byref(st), ctypes.byref(st2))
+        del keep
+        return st, st2
 
     def round(self, store_root: str, ntargets: int, events: "EventSet", cum_weight=None, log=None):
         """bcp_gen_round_pipeline: plan from events + DB, run batched, update the DB."""

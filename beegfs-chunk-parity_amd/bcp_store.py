@@ -5,6 +5,7 @@ its chunk files, README.md of the reference):
 
     <root>/st<k>/chunks/<relative path>   chunk file of target k
     <root>/st<k>/parity/<relative path>   parity chunk file written by P
+    <root>/st<k>/parityq/<relative path>  Q parity file (pipeline runs with Q on)
 
 A work item is (path, timestamp, locations) with locations = chunk-holder
 bitmask | P << 56 (common.h:19-25).
@@ -37,6 +38,11 @@ def chunk_path(root: str, st: int, path: str) -> str:
 
 def parity_path(root: str, st: int, path: str) -> str:
     return os.path.join(root, f"st{st}", "parity", path)
+
+
+def parityq_path(root: str, st: int, path: str) -> str:
+    """The Q file of an item whose Q target (bcp_ctypes.q_target) is st."""
+    return os.path.join(root, f"st{st}", "parityq", path)
 
 
 def write_chunk(root: str, st: int, path: str, data) -> None:

@@ -42,7 +42,7 @@ struct bcp_engine {
   pthread_mutex_t lock = PTHREAD_MUTEX_INITIALIZER;
   std::atomic<int> last_stream_vecs{0};  // U of the latest xor_stream launch (tools)
   std::atomic<int> last_desc_vecs{0};    // U of the latest descriptor-kernel launch (tools)
-  std::atomic<int> last_desc_form{0};    // 1 xor_desc (desc_tiles), 2 xor_desc_args, 3 check_desc
+  std::atomic<int> last_desc_form{0};    // 1 xor_desc (desc_tiles), 2 xor_desc_args, 3 check_desc, 4 / 5 pq_desc gen / solve
 };
 
 namespace {
@@ -360,6 +360,7 @@ extern "C" int bcp_set_option(bcp_engine *eng, const char *key, int value) {
     eng->tuning.desc_table_host_max = value;
   else if (!strcmp(key, "ring_spin_us") && value >= 0 && value <= 1000000) eng->tuning.ring_spin_us = value;
   else if (!strcmp(key, "ring_sleep_us") && value >= 0 && value <= 100000) eng->tuning.ring_sleep_us = value;
+  else if (!strcmp(key, "pq_blocks_per_cu") && value >= 1 && value <= 8) eng->tuning.pq_blocks_per_cu = value;
   else rc = -EINVAL;
   pthread_mutex_unlock(&eng->lock);
   return rc;
@@ -384,6 +385,7 @@ extern "C" int bcp_get_option(bcp_engine *eng, const char *key, int *value) {
   else if (!strcmp(key, "desc_table_host_max")) *value = t.desc_table_host_max;
   else if (!strcmp(key, "ring_spin_us")) *value = t.ring_spin_us;
   else if (!strcmp(key, "ring_sleep_us")) *value = t.ring_sleep_us;
+  else if (!strcmp(key, "pq_blocks_per_cu")) *value = t.pq_blocks_per_cu;
   else if (!strcmp(key, "last_stream_vecs")) *value = eng->last_stream_vecs.load(std::memory_order_relaxed);
   else if (!strcmp(key, "last_desc_vecs")) *value = eng->last_desc_vecs.load(std::memory_order_relaxed);
   else if (!strcmp(key, "last_desc_form")) *value = eng->last_desc_form.load(std::memory_order_relaxed);
@@ -1195,6 +1197,178 @@ extern "C" int bcp_check_stripes_async(bcp_queue *q, const bcp_stripe *stripes, 
   int rc = set_device(q->eng);
   if (rc) return rc;
   return submit_desc(q, stripes, nstripes, sources, nsources, results_dev);
+}
+
+// ---------------------------------------------------------------------------
+// P + Q parity (bcp_pq.hip).  GF(2^8), polynomial 0x11d, generator 2.
+// ---------------------------------------------------------------------------
+namespace {
+struct Gf256 {
+  uint8_t exp[510];
+  uint8_t log[256];
+  Gf256() {
+    unsigned x = 1;
+    for (int i = 0; i < 255; i++) {
+      exp[i] = exp[i + 255] = (uint8_t)x;
+      log[x] = (uint8_t)i;
+      x <<= 1;
+      if (x & 0x100) x ^= 0x11d;
+    }
+    log[0] = 0;
+  }
+  uint8_t pow(int e) const { return exp[((e % 255) + 255) % 255]; }
+  uint8_t div(uint8_t a, uint8_t b) const { return a ? exp[log[a] + 255 - log[b]] : 0; }  // b != 0
+};
+const Gf256 g_gf;
+}  // namespace
+
+// Both forms: `lost` == nullptr is GEN (q_dst gives the Q bodies), else SOLVE.
+// The staged tables are the stripes' records, their source runs copied in the
+// caller's order, and one record per tile; they go through stage_tables with
+// the pointer-table threshold, since the kernel reads them once per tile.
+static int submit_pq(bcp_queue *q, const bcp_stripe *stripes, uint32_t nstripes, const bcp_source *sources,
+                     uint32_t nsources, const uint64_t *q_dst, const bcp_pq_lost *lost) {
+  bcp_engine *e = q->eng;
+  uint64_t tiles8 = 0, nstaged = 0;
+  for (uint32_t i = 0; i < nstripes; i++) {
+    const bcp_stripe &s = stripes[i];
+    if (s.window != 0 || s.nsrc > BCP_MAX_SOURCES) return -EINVAL;
+    if ((uint64_t)s.first_src + s.nsrc > nsources) return -EINVAL;
+    for (uint32_t k = 0; k < s.nsrc; k++) {
+      const bcp_source &x = sources[s.first_src + k];
+      if (x.len && !x.ptr) return -EINVAL;
+    }
+    uint64_t cover = s.out_len;  // output bytes the tiles have to cover
+    if (lost) {
+      const bcp_pq_lost &l = lost[i];
+      const bool two = l.y != BCP_PQ_NONE;
+      if (l.x >= s.nsrc || (two && (l.y <= l.x || l.y >= s.nsrc))) return -EINVAL;
+      if ((l.p != 0) != two) return -EINVAL;  // P present with one loss is RAID-5; P lost leaves Q for one member
+      if (s.out_len && !l.q) return -EINVAL;
+      if (sources[s.first_src + l.x].len != 0 || (two && sources[s.first_src + l.y].len != 0)) return -EINVAL;
+      if (l.len_x > s.out_len || (two && l.len_y > s.out_len)) return -EINVAL;
+      if ((l.len_x && !l.dst_x) || (two && l.len_y && !l.dst_y)) return -EINVAL;
+      cover = std::max(l.len_x, two ? l.len_y : (uint64_t)0);
+    } else if (s.out_len && !q_dst[i]) {
+      return -EINVAL;
+    }
+    tiles8 += (cover + desc_tile_bytes(8) - 1) / desc_tile_bytes(8);
+    nstaged += s.nsrc;
+  }
+  if (tiles8 > 0xFFFFFFF0ull / 4 || nstaged > 0xFFFFFFFFull) return -EINVAL;
+  if (tiles8 == 0) return 0;
+  int vecs = e->tuning.desc_vecs;
+  // 16 KiB tiles unless asked otherwise: at 4 vectors per lane the kernel keeps three waves per
+  // SIMD, whose arithmetic hides under the others' loads; at 8 it runs one (tools/pq_rate.py)
+  if (!pq_vecs_ok(vecs)) vecs = 4;
+  const uint32_t T = desc_tile_bytes(vecs);
+  auto tiles_of = [&](uint32_t i) -> uint64_t {
+    uint64_t cover = stripes[i].out_len;
+    if (lost) cover = std::max(lost[i].len_x, lost[i].y != BCP_PQ_NONE ? lost[i].len_y : (uint64_t)0);
+    return (cover + T - 1) / T;
+  };
+  uint64_t ntiles64 = 0;
+  for (uint32_t i = 0; i < nstripes; i++) ntiles64 += tiles_of(i);
+  if (ntiles64 > 0xFFFFFFF0ull) return -EINVAL;
+  const uint32_t ntiles = (uint32_t)ntiles64;
+  const size_t off_src = (size_t)nstripes * sizeof(PqStripe);
+  const size_t off_tiles = (off_src + (size_t)nstaged * sizeof(bcp_source) + 15) & ~(size_t)15;
+  const size_t bytes = off_tiles + (size_t)ntiles * sizeof(PqTile);
+  DescSlot *slot = nullptr;
+  int rc = ring_acquire(q, bytes, &slot);
+  if (rc) return rc;
+  slot->rec_ok = false;  // its tables are about to be overwritten
+  char *h = (char *)slot->host;
+  PqStripe *hs = (PqStripe *)h;
+  bcp_source *hso = (bcp_source *)(h + off_src);
+  PqTile *ht = (PqTile *)(h + off_tiles);
+  // prefix sums first, so that the records can be written by several threads
+  std::vector<uint32_t> tile0(nstripes);
+  {
+    uint32_t next_src = 0, next_tile = 0;
+    for (uint32_t i = 0; i < nstripes; i++) {
+      hs[i].first_src = next_src;
+      next_src += stripes[i].nsrc;
+      tile0[i] = next_tile;
+      next_tile += (uint32_t)tiles_of(i);
+    }
+  }
+  par_for(nstripes, 1024, [&](uint32_t lo, uint32_t hi) {
+    for (uint32_t i = lo; i < hi; i++) {
+      const bcp_stripe &s = stripes[i];
+      PqStripe r{};
+      r.first_src = hs[i].first_src;
+      r.nsrc = s.nsrc;
+      r.out_len = s.out_len;
+      if (lost) {
+        const bcp_pq_lost &l = lost[i];
+        const bool two = l.y != BCP_PQ_NONE;
+        r.p = l.p;
+        r.q = l.q;
+        r.dx = l.dst_x;
+        r.len_x = l.len_x;
+        r.dy = two ? l.dst_y : 0;
+        r.len_y = two ? l.len_y : 0;
+        if (two) {
+          // D_x = A * Ps ^ B * Qs with d = g^(y-x) ^ 1, A = g^(y-x) / d, B = g^(-x) / d
+          const uint8_t gyx = g_gf.pow((int)(l.y - l.x)), dd = (uint8_t)(gyx ^ 1);
+          r.ca = g_gf.div(gyx, dd);
+          r.cb = g_gf.div(g_gf.pow(-(int)l.x), dd);
+        } else {
+          r.ca = 0;  // P lost: D_x = g^(-x) * Qs
+          r.cb = g_gf.pow(-(int)l.x);
+        }
+      } else {
+        r.p = s.dst;
+        r.q = q_dst[i];
+      }
+      hs[i] = r;
+      if (s.nsrc) memcpy(hso + r.first_src, sources + s.first_src, (size_t)s.nsrc * sizeof(bcp_source));
+      const uint32_t n = (uint32_t)tiles_of(i);
+      for (uint32_t j = 0; j < n; j++) ht[tile0[i] + j] = PqTile{i, j};
+    }
+  });
+  char *d = nullptr;
+  if ((rc = stage_tables(q, slot, bytes, (size_t)e->tuning.table_host_max, &d))) return rc;
+  PqBatch b;
+  b.stripes = (const PqStripe *)d;
+  b.sources = (const bcp_source *)(d + off_src);
+  b.tiles = (const PqTile *)(d + off_tiles);
+  b.ntiles = ntiles;
+  b.ctr = q->qctr;
+  b.base = q->qbase;
+  int grid = e->tuning.desc_grid > 0 ? e->tuning.desc_grid : e->num_cus * e->tuning.pq_blocks_per_cu;
+  if (grid <= 0) grid = 256;
+  if ((uint32_t)grid > ntiles) grid = (int)ntiles;
+  if (q->broken) return -EIO;
+  (void)hipGetLastError();  // see launch_stream
+  const hipError_t le = launch_pq(q->stream, grid, vecs, lost != nullptr, b);
+  if (le == hipSuccess) {
+    e->last_desc_vecs.store(vecs, std::memory_order_relaxed);
+    e->last_desc_form.store(lost ? 5 : 4, std::memory_order_relaxed);
+  }
+  if ((rc = queue_launched(q, le, (uint64_t)ntiles + (uint64_t)grid))) return rc;
+  HIP_RC(hipEventRecord(slot->done, q->stream));
+  slot->used = true;
+  return 0;
+}
+
+extern "C" int bcp_pq_stripes_async(bcp_queue *q, const bcp_stripe *stripes, uint32_t nstripes,
+                                    const bcp_source *sources, uint32_t nsources, const uint64_t *q_dst) {
+  if (!q || !stripes || !q_dst || (nsources && !sources)) return -EINVAL;
+  if (!nstripes) return 0;
+  int rc = set_device(q->eng);
+  if (rc) return rc;
+  return submit_pq(q, stripes, nstripes, sources, nsources, q_dst, nullptr);
+}
+
+extern "C" int bcp_pq_recover_stripes_async(bcp_queue *q, const bcp_stripe *stripes, uint32_t nstripes,
+                                            const bcp_source *sources, uint32_t nsources, const bcp_pq_lost *lost) {
+  if (!q || !stripes || !lost || (nsources && !sources)) return -EINVAL;
+  if (!nstripes) return 0;
+  int rc = set_device(q->eng);
+  if (rc) return rc;
+  return submit_pq(q, stripes, nstripes, sources, nsources, nullptr, lost);
 }
 
 extern "C" int bcp_xor_strided_async(bcp_queue *q, void *dst, uint64_t dst_stride, const void *src,

@@ -51,6 +51,8 @@ struct Tuning {
     // this long between looks (0: sched_yield instead).
     int ring_spin_us = 4;
     int ring_sleep_us = 10;
+    // pq_desc (P + Q parity): workgroups per CU (tools/pq_rate.py).
+    int pq_blocks_per_cu = 2;
 };
 
 // Arguments of the streaming kernel (xor_stream).
@@ -273,6 +275,38 @@ struct RingArgs {
     unsigned long long hard_ticks;   // worker: give up waiting after this long (no watcher)
     uint32_t kmask, kshift;          // K - 1, log2 K
 };
+
+// ---------------------------------------------------------------------------
+// P + Q parity (bcp_pq.hip; bcp_pq_stripes_async, bcp_pq_recover_stripes_async).
+// One record per stripe and one per tile, both written by the host: the
+// sources of a run stay in the caller's position order (source k has
+// coefficient g^k), so nothing here is sorted.
+// ---------------------------------------------------------------------------
+struct alignas(16) PqStripe {
+    uint64_t p, q;          // GEN: P / Q output (p 0: no P); SOLVE: P / Q body (p 0: P is lost)
+    uint64_t out_len;       // GEN: bytes of each output; SOLVE: readable bytes of p and q
+    uint32_t first_src, nsrc;
+    uint64_t dx, len_x;     // SOLVE: member x, its first len_x bytes
+    uint64_t dy, len_y;     // SOLVE: member y (len_y 0: not asked for)
+    uint32_t ca, cb;        // SOLVE: D_x = ca * Ps ^ cb * Qs over GF(2^8)
+    uint32_t pad[2];
+};
+static_assert(sizeof(PqStripe) == 80, "five 16-byte scalar loads");
+struct PqTile {
+    uint32_t stripe, sub;   // bytes [sub * T, (sub + 1) * T) of the stripe's outputs
+};
+struct PqBatch {
+    const PqStripe *stripes;
+    const bcp_source *sources;  // staged runs, position order
+    const PqTile *tiles;        // [ntiles]
+    uint32_t ntiles;
+    unsigned long long *ctr;    // work-queue counter (per queue), as StreamArgs
+    unsigned long long base;
+};
+inline bool pq_vecs_ok(int v) { return v == 4 || v == 8; }
+// GEN (solve = false) or SOLVE form, vecs 4 or 8 (tile = desc_tile_bytes(vecs));
+// same work-queue accounting as launch_xor_stream (ntiles + grid).
+hipError_t launch_pq(hipStream_t st, int grid, int vecs, bool solve, const PqBatch &b);
 
 // Kernel launchers (bcp_kernels.hip).  All return hipError_t.
 // Streaming fold.  Consumes ceil(ntiles / grab) + grid counts of a.ctr; the

@@ -38,6 +38,14 @@
  * where it lies in the input slab (bcp_check_stripes_async), 16 bytes per item
  * come back in the output slab, and the completion stage turns them into
  * verdicts.  No write jobs, nothing under the store changes.
+ *
+ * Q parity (bcp_pipeline_set_q_parity, bcp_pipeline_rebuild2; bcp_task.h): a
+ * task may have a second output, placed after the first in the output slab
+ * and written by a second write job -- the Q body of a gen task (file
+ * <root>/st<q>/parityq/<path>, same header), or the second chunk of a rebuild
+ * from P and Q.  Those tasks' stripes go in a launch of their own per batch
+ * (bcp_pq_stripes_async / bcp_pq_recover_stripes_async, sources in holder
+ * order) beside the batch's bcp_xor_stripes_async.
  */
 #define _GNU_SOURCE
 #include <errno.h>
@@ -246,20 +254,50 @@ typedef struct {
     size_t item;                         /* verify: index of the work item */
     uint32_t status;                     /* verify: BCP_VERIFY_* or VERIFY_PENDING */
     uint64_t first_bad, bad_bytes;       /* verify: the device's record */
+    /* Q parity.  gen: q_st is the item's Q target when the run writes its Q
+     * file (-1: none).  rebuild2: pq = 1 recovers the victim from Q alone (P is
+     * lost too), pq = 2 both victims (p, p2) from P and Q; the sources are then
+     * the survivors, ascending, src_pos[k] their position among the item's
+     * `width` holders, followed by the P body (pq = 2, parity_src) and the Q
+     * body (q_src). */
+    int q_st;
+    int pq;
+    int p2;                              /* pq = 2: the second victim */
+    int width;                           /* pq: holders of the item = header entries */
+    int lost_pos[2];                     /* pq: positions of the victims */
+    int src_pos[MAX_STORAGE_TARGETS];    /* pq: position of survivor k */
+    int q_src;                           /* pq: index of the Q body among the sources */
+    int unrecov;                         /* pq, after the stat phase: cannot be recovered */
+    int has2;                            /* a second output: the Q body (gen), the second chunk (pq = 2) */
+    uint64_t out_len2;
+    int prealloc2;
+    uint64_t header[MAX_STORAGE_TARGETS];/* pq: the sizes header of the parity files */
 } task;
 
 #define VERIFY_PENDING 0xFFu             /* passed the stat phase: to be read and compared */
 
-/* Source k is read from the parity directory, after the u64 header. */
-static int src_is_parity(const task *t, int k)
+/* Where source k is read from: 0 the chunks directory, 1 the parity directory
+ * and 2 the Q parity directory (both after the u64 header). */
+static const char *const k_dir[3] = {"chunks", "parity", "parityq"};
+static int src_kind(const task *t, int k)
 {
+    if (t->pq && k == t->q_src)
+        return 2;
     return (t->rebuild || t->verify) && k == t->parity_src;
 }
 
-/* Bytes a task takes in the output slab. */
+/* Bytes a task takes in the output slab; a second output follows the first
+ * at the next multiple of 256. */
+static uint64_t out_off2(const task *t)
+{
+    return t->out_off + (t->out_len + 255u) / 256u * 256u;
+}
+
 static uint64_t out_span(const task *t)
 {
-    return t->verify ? sizeof(bcp_check_result) : (t->out_len + 255u) / 256u * 256u;
+    if (t->verify)
+        return sizeof(bcp_check_result);
+    return (t->out_len + 255u) / 256u * 256u + (t->has2 ? (t->out_len2 + 255u) / 256u * 256u : 0);
 }
 
 typedef struct {
@@ -325,6 +363,7 @@ typedef struct {
     FILE *log;
     int *errors;
     int prealloc;         /* posix_fallocate first (not on tmpfs: see do_write) */
+    int second;           /* the task's second output (Q file / second rebuilt chunk) */
 } write_arg;
 
 typedef struct {
@@ -332,7 +371,7 @@ typedef struct {
     slot *S;
     const char *root;
     task *tasks;
-    write_arg *wa;        /* one per task of the run */
+    write_arg *wa;        /* two per task of the run (the second: task.has2) */
     size_t first, last;
     pool *io;
     FILE *log;
@@ -409,6 +448,63 @@ static void do_stat(job *p)
         latch_down(a->done);
         return;
     }
+    if (t->pq) {
+        /* rebuild2 from Q (and P): the parity files' headers and sizes decide
+         * whether the item can be recovered at all */
+        const int w = t->width;
+        uint64_t hq[MAX_STORAGE_TARGETS] = {0};
+        int ok = 1;
+        for (int pass = 0; pass < 2; pass++) {
+            const int k = pass ? t->q_src : t->parity_src;
+            if (k < 0)
+                continue;
+            uint64_t *h = pass ? hq : t->header;
+            uint64_t fsize = 0, m = 0;
+            struct stat st;
+            chunk_file(fn, sizeof(fn), a->root, t->holders[k], k_dir[src_kind(t, k)], t->path);
+            int fd = open(fn, O_RDONLY);
+            int have = 0;
+            if (fd >= 0) {
+                if (fstat(fd, &st) == 0)
+                    fsize = (uint64_t)st.st_size;
+                have = fsize >= (uint64_t)w * 8u && pread(fd, h, (size_t)w * 8u, 0) == (ssize_t)((size_t)w * 8u);
+                close(fd);
+            }
+            for (int j = 0; j < w; j++)
+                if (h[j] > m)
+                    m = h[j];
+            ok = ok && have && fsize == (uint64_t)w * 8u + m;
+        }
+        if (t->parity_src < 0)
+            memcpy(t->header, hq, sizeof(hq));
+        else
+            ok = ok && memcmp(t->header, hq, (size_t)w * 8u) == 0;
+        for (int j = 0; j < w; j++)
+            if (t->header[j] > t->max_cs)
+                t->max_cs = t->header[j];
+        ok = ok && t->max_cs <= WINDOW; /* windowed items have no Q */
+        for (int k = 0; k < t->n; k++) {
+            struct stat st;
+            if (k == t->parity_src || k == t->q_src) {
+                t->src_off[k] = (uint64_t)w * 8u;
+                t->size[k] = ok ? t->max_cs : 0;
+                continue;
+            }
+            chunk_file(fn, sizeof(fn), a->root, t->holders[k], "chunks", t->path);
+            t->src_off[k] = 0;
+            t->size[k] = 0;
+            if (stat(fn, &st) == 0) {
+                t->size[k] = (uint64_t)st.st_size > t->max_cs ? t->max_cs : (uint64_t)st.st_size;
+                if (st.st_mtime > t->timestamp)
+                    push_corrupt(a->corrupt_fd, t->path);
+            }
+        }
+        t->out_len = t->header[t->lost_pos[0]];
+        t->out_len2 = t->pq == 2 ? t->header[t->lost_pos[1]] : 0;
+        t->unrecov = !ok;
+        latch_down(a->done);
+        return;
+    }
     if (!t->rebuild) {
         for (int k = 0; k < t->n; k++) {
             chunk_file(fn, sizeof(fn), a->root, t->holders[k], "chunks", t->path);
@@ -419,6 +515,14 @@ static void do_stat(job *p)
                 t->max_cs = t->size[k];
         }
         t->out_len = t->max_cs;
+        if (t->q_st >= 0 && t->max_cs > WINDOW) {
+            /* windowed: P only; a Q file from an earlier, smaller state goes */
+            chunk_file(fn, sizeof(fn), a->root, t->q_st, "parityq", t->path);
+            unlink(fn);
+            t->q_st = -2;
+        }
+        t->has2 = t->q_st >= 0;
+        t->out_len2 = t->max_cs;
         latch_down(a->done);
         return;
     }
@@ -479,7 +583,7 @@ static void do_read(job *p)
     int direct = 0, fell_back = 0;
     if (want) {
         char fn[4352];
-        chunk_file(fn, sizeof(fn), a->root, t->holders[a->k], src_is_parity(t, a->k) ? "parity" : "chunks", t->path);
+        chunk_file(fn, sizeof(fn), a->root, t->holders[a->k], k_dir[src_kind(t, a->k)], t->path);
         int fd = -1;
         if (a->direct) {
             fd = open(fn, O_RDONLY | O_DIRECT);
@@ -566,7 +670,11 @@ static void do_write(job *p)
     write_arg *a = (write_arg *)p;
     task *t = a->t;
     char fn[4352];
-    chunk_file(fn, sizeof(fn), a->root, t->p, t->rebuild ? "chunks" : "parity", t->path);
+    /* the second output: the Q file of a gen task, the second chunk of a
+     * two-victim rebuild */
+    const int out_st = !a->second ? t->p : t->rebuild ? t->p2 : t->q_st;
+    const uint64_t out_len = a->second ? t->out_len2 : t->out_len;
+    chunk_file(fn, sizeof(fn), a->root, out_st, t->rebuild ? "chunks" : a->second ? "parityq" : "parity", t->path);
     /* directories only when the file cannot be created (mkdir_for_file,
      * task_processing.c:30-40, does every level first: a lookup per level
      * per file).  (Overwriting an existing file in place instead of
@@ -581,7 +689,7 @@ static void do_write(job *p)
     if (!bad) {
         /* gen: u64 sizes header + body; rebuild: the chunk itself */
         const size_t hdr = t->rebuild ? 0 : 8u * (size_t)t->n;
-        uint64_t total = hdr + t->out_len;
+        uint64_t total = hdr + out_len;
         /* The reference reserves the file's space first (task_processing.c:186):
          * on a disk that keeps it in one extent and fails early when full.  On
          * tmpfs it makes the kernel allocate and ZERO every page before the
@@ -589,7 +697,7 @@ static void do_write(job *p)
          * nothing -- so it is skipped there (the file is the same). */
         if (total && a->prealloc)
             posix_fallocate(fd, 0, (off_t)total);
-        struct iovec iov[2] = {{t->size, hdr}, {(void *)a->body, (size_t)t->out_len}};
+        struct iovec iov[2] = {{t->size, hdr}, {(void *)a->body, (size_t)out_len}};
         uint64_t done = 0;
         int idx = total ? 0 : 2; /* an empty rebuilt chunk: nothing to write */
         while (idx < 2 && !bad) {
@@ -656,13 +764,22 @@ static void do_complete(job *p)
         *a.dev_rc = rc;
         pthread_mutex_unlock(&g_stat_lock);
         for (size_t i = a.first; i < a.last; i++)
-            latch_down(&a.S->writes);
+            for (int o = 0; o <= a.tasks[i].has2; o++)
+                latch_down(&a.S->writes);
     } else {
         for (size_t i = a.first; i < a.last; i++) {
-            write_arg *w = &a.wa[i];
+            /* (has2 read before the first job is handed over: see above) */
+            const int has2 = a.tasks[i].has2;
+            const uint64_t off2 = out_off2(&a.tasks[i]);
+            const int pre2 = a.tasks[i].prealloc2;
+            write_arg *w = &a.wa[2 * i];
             *w = (write_arg){{0}, a.root, &a.tasks[i], a.S->h_out + a.tasks[i].out_off, &a.S->writes, a.log, a.errors,
-                             a.tasks[i].prealloc};
+                             a.tasks[i].prealloc, 0};
+            if (has2)
+                w[1] = (write_arg){{0}, a.root, &a.tasks[i], a.S->h_out + off2, &a.S->writes, a.log, a.errors, pre2, 1};
             pool_push(a.io, &w->j, do_write);
+            if (has2)
+                pool_push(a.io, &w[1].j, do_write);
         }
     }
 }
@@ -712,7 +829,14 @@ struct bcp_pipeline {
     size_t in_cap, out_cap;
     bcp_stripe *st;
     bcp_source *so;
+    bcp_stripe *st2;    /* the batch's P + Q stripes (a launch of their own) */
+    bcp_source *so2;
+    uint64_t *qd;
+    bcp_pq_lost *lost;
     size_t desc_cap;    /* stripes the descriptor arrays hold */
+    int q_on;           /* bcp_pipeline_set_q_parity */
+    uint64_t q_written, q_no_target, q_windowed; /* of the last run */
+    uint8_t *r2_unrec;  /* during a rebuild2 run: per item, 1 = unrecoverable after the stat phase */
     bcp_pipeline_timing last; /* of the last run */
 };
 
@@ -767,6 +891,10 @@ int bcp_pipeline_destroy(bcp_pipeline *pl)
     }
     free(pl->st);
     free(pl->so);
+    free(pl->st2);
+    free(pl->so2);
+    free(pl->qd);
+    free(pl->lost);
     free(pl);
     return 0;
 }
@@ -970,15 +1098,21 @@ int bcp_pipeline_run(bcp_pipeline *pl, const char *store_root, int ntargets, con
                 fprintf(log, "bcp_pipeline: refusing '%s': not a path inside the store\n", items[i].path);
             continue;
         }
+        const int qt = pl->q_on ? bcp_q_target(loc, ntargets) : -1;
         if ((loc & L_MASK) == 0) {
             char fn[4352];
             chunk_file(fn, sizeof(fn), store_root, P, "parity", items[i].path);
             unlink(fn);
+            if (qt >= 0) {
+                chunk_file(fn, sizeof(fn), store_root, qt, "parityq", items[i].path);
+                unlink(fn);
+            }
             continue;
         }
         task *t = &tasks[nt++];
         t->path = items[i].path;
         t->p = P;
+        t->q_st = qt;
         for (int k = 0; k < MAX_STORAGE_TARGETS; k++)
             if (TEST_BIT(loc, k))
                 t->holders[t->n++] = k;
@@ -1010,15 +1144,15 @@ typedef struct {
  * once per run: <root>/st<k>/{chunks,parity} are often separate mounts, so
  * the choices below are made per target, never from the store root. */
 typedef struct {
-    signed char mem[MAX_STORAGE_TARGETS][2]; /* [k][0 chunks, 1 parity]: 1 tmpfs / ramfs, 0 not, -1 unknown yet */
+    signed char mem[MAX_STORAGE_TARGETS][3]; /* [k][0 chunks, 1 parity, 2 parityq]: 1 tmpfs / ramfs, 0 not, -1 unknown yet */
 } fs_kinds;
 
-static int dir_in_memory(fs_kinds *fk, const char *root, int k, int parity)
+static int dir_in_memory(fs_kinds *fk, const char *root, int k, int kind)
 {
-    signed char *m = &fk->mem[k][parity];
+    signed char *m = &fk->mem[k][kind];
     if (*m < 0) {
         char dn[4352];
-        snprintf(dn, sizeof(dn), "%s/st%d/%s", root, k, parity ? "parity" : "chunks");
+        snprintf(dn, sizeof(dn), "%s/st%d/%s", root, k, k_dir[kind]);
         struct statfs sf;
         *m = statfs(dn, &sf) == 0 && (sf.f_type == TMPFS_MAGIC || sf.f_type == RAMFS_MAGIC);
     }
@@ -1037,7 +1171,7 @@ static int auto_read_mode(const char *root, const task *tasks, size_t nt, fs_kin
     int all_mem = 1;
     for (size_t i = 0; i < nt && all_mem; i++)
         for (int k = 0; k < tasks[i].n && all_mem; k++)
-            all_mem = dir_in_memory(fk, root, tasks[i].holders[k], src_is_parity(&tasks[i], k));
+            all_mem = dir_in_memory(fk, root, tasks[i].holders[k], src_kind(&tasks[i], k));
     if (all_mem)
         return BCP_READ_COPY;
     const uint64_t cap = (uint64_t)16 << 20;
@@ -1051,7 +1185,7 @@ static int auto_read_mode(const char *root, const task *tasks, size_t nt, fs_kin
         for (int k = 0; k < t->n; k++) {
             if (!t->size[k])
                 continue;
-            chunk_file(fn, sizeof(fn), root, t->holders[k], src_is_parity(t, k) ? "parity" : "chunks", t->path);
+            chunk_file(fn, sizeof(fn), root, t->holders[k], k_dir[src_kind(t, k)], t->path);
             const uint64_t len = t->src_off[k] + t->size[k] < cap ? t->src_off[k] + t->size[k] : cap;
             int fd = open(fn, O_RDONLY);
             if (fd < 0)
@@ -1121,10 +1255,39 @@ static int pipeline_exec(bcp_pipeline *pl, const char *store_root, task *tasks, 
         }
         nt = w;
     }
+    if (pl->r2_unrec) {
+        /* rebuild2: the items that cannot be recovered drop out (order kept);
+         * nothing is read or written for them */
+        size_t w = 0;
+        for (size_t i = 0; i < nt; i++) {
+            if (tasks[i].unrecov) {
+                pl->r2_unrec[tasks[i].item] = 1;
+                continue;
+            }
+            if (w != i)
+                tasks[w] = tasks[i];
+            w++;
+        }
+        nt = w;
+    }
     /* the reference reserves every output's space first (task_processing.c:186),
      * except where that output's directory is tmpfs / ramfs (do_write) */
-    for (size_t i = 0; i < nt && !verify; i++)
+    for (size_t i = 0; i < nt && !verify; i++) {
         tasks[i].prealloc = !dir_in_memory(&fk, store_root, tasks[i].p, !tasks[i].rebuild);
+        if (tasks[i].rebuild)
+            tasks[i].has2 = tasks[i].pq == 2;
+        if (tasks[i].has2)
+            tasks[i].prealloc2 = !dir_in_memory(&fk, store_root, tasks[i].rebuild ? tasks[i].p2 : tasks[i].q_st,
+                                                tasks[i].rebuild ? 0 : 2);
+    }
+    /* Q files of the run (bcp_pipeline_q_stats) */
+    pl->q_written = pl->q_no_target = pl->q_windowed = 0;
+    for (size_t i = 0; i < nt && pl->q_on && !verify; i++)
+        if (!tasks[i].rebuild) {
+            pl->q_written += tasks[i].q_st >= 0;
+            pl->q_no_target += tasks[i].q_st == -1;
+            pl->q_windowed += tasks[i].q_st == -2;
+        }
 
     /* 2. plan batches: inputs at 256-byte pitch (DIRECT: page pitch), outputs
      * at 256 */
@@ -1211,9 +1374,18 @@ static int pipeline_exec(bcp_pipeline *pl, const char *store_root, task *tasks, 
     if (pl->desc_cap < nt) {
         free(pl->st);
         free(pl->so);
+        free(pl->st2);
+        free(pl->so2);
+        free(pl->qd);
+        free(pl->lost);
         pl->st = malloc((nt ? nt : 1) * sizeof(bcp_stripe));
         pl->so = malloc((nt ? nt : 1) * MAX_STORAGE_TARGETS * sizeof(bcp_source));
-        pl->desc_cap = (pl->st && pl->so) ? nt : 0;
+        /* the batch's P + Q stripes (gen with Q, rebuild2) go in a launch of their own */
+        pl->st2 = malloc((nt ? nt : 1) * sizeof(bcp_stripe));
+        pl->so2 = malloc((nt ? nt : 1) * MAX_STORAGE_TARGETS * sizeof(bcp_source));
+        pl->qd = malloc((nt ? nt : 1) * sizeof(uint64_t));
+        pl->lost = malloc((nt ? nt : 1) * sizeof(bcp_pq_lost));
+        pl->desc_cap = (pl->st && pl->so && pl->st2 && pl->so2 && pl->qd && pl->lost) ? nt : 0;
         if (!pl->desc_cap) {
             return -ENOMEM;
         }
@@ -1227,7 +1399,7 @@ static int pipeline_exec(bcp_pipeline *pl, const char *store_root, task *tasks, 
         for (int k = 0; k < tasks[i].n; k++)
             nreads_all += (size_t)pieces_of(read_extent(&tasks[i], k, dir));
     read_arg *ra = calloc(nreads_all ? nreads_all : 1, sizeof(read_arg));
-    write_arg *wa = calloc(nt ? nt : 1, sizeof(write_arg));
+    write_arg *wa = calloc(nt ? 2 * nt : 1, sizeof(write_arg));
     complete_arg *cargs = calloc(nbatches ? (size_t)nbatches : 1, sizeof(complete_arg));
     bstate *bs = calloc(nbatches ? (size_t)nbatches : 1, sizeof(bstate));
     if (!ra || !wa || !cargs || !bs) {
@@ -1307,10 +1479,49 @@ static int pipeline_exec(bcp_pipeline *pl, const char *store_root, task *tasks, 
         B->reads_live = 0;
         const double ts = now_s();
         tm.read_wait += ts - t_wait0; /* blocked on this batch's reads */
-        uint32_t ns = 0, nsrc = 0;
+        uint32_t ns = 0, nsrc = 0, ns2 = 0, nsrc2 = 0;
         uint64_t out_used = 0;
+        long nwrites = 0;
+        int recover = 0;
         for (size_t i = first; i < last; i++) {
             task *t = &tasks[i];
+            nwrites += 1 + t->has2;
+            if (t->pq) {
+                /* the survivors in position order, the victims' positions empty */
+                recover = 1;
+                bcp_pq_lost *l = &pl->lost[ns2];
+                memset(l, 0, sizeof(*l));
+                l->p = t->parity_src >= 0 ? (uint64_t)S->d_in + data_off(t, t->parity_src, dir) : 0;
+                l->q = (uint64_t)S->d_in + data_off(t, t->q_src, dir);
+                l->x = (uint32_t)t->lost_pos[0];
+                l->y = t->pq == 2 ? (uint32_t)t->lost_pos[1] : BCP_PQ_NONE;
+                l->dst_x = (uint64_t)S->d_out + t->out_off;
+                l->len_x = t->out_len;
+                l->dst_y = (uint64_t)S->d_out + out_off2(t);
+                l->len_y = t->out_len2;
+                pl->st2[ns2] = (bcp_stripe){0, t->max_cs, nsrc2, (uint32_t)t->width, 0};
+                for (int j = 0; j < t->width; j++)
+                    pl->so2[nsrc2 + j] = (bcp_source){0, 0};
+                for (int k = 0; k < t->n; k++)
+                    if (k != t->parity_src && k != t->q_src)
+                        pl->so2[nsrc2 + t->src_pos[k]] = (bcp_source){(uint64_t)S->d_in + data_off(t, k, dir), t->size[k]};
+                nsrc2 += (uint32_t)t->width;
+                ns2++;
+                if (t->out_off + out_span(t) > out_used)
+                    out_used = t->out_off + out_span(t);
+                continue;
+            }
+            if (t->has2) {
+                /* gen with a Q file: P and Q in one pass, sources in holder order */
+                pl->st2[ns2] = (bcp_stripe){(uint64_t)S->d_out + t->out_off, t->out_len, nsrc2, (uint32_t)t->n, 0};
+                pl->qd[ns2] = (uint64_t)S->d_out + out_off2(t);
+                for (int k = 0; k < t->n; k++)
+                    pl->so2[nsrc2++] = (bcp_source){(uint64_t)S->d_in + data_off(t, k, dir), t->size[k]};
+                ns2++;
+                if (t->out_off + out_span(t) > out_used)
+                    out_used = t->out_off + out_span(t);
+                continue;
+            }
             /* verify: dst is the parity body in the input slab (only read), the
              * sources are the chunks before it */
             const int nfold = verify ? t->n - 1 : t->n;
@@ -1327,6 +1538,8 @@ static int pipeline_exec(bcp_pipeline *pl, const char *store_root, task *tasks, 
             (rc = bcp_event_record(S->ev_h, L->qh)) || (rc = bcp_queue_wait_event(L->qk, S->ev_h)) ||
             (rc = verify ? bcp_check_stripes_async(L->qk, st, ns, so, nsrc, (bcp_check_result *)S->d_out)
                          : bcp_xor_stripes_async(L->qk, st, ns, so, nsrc)) ||
+            (ns2 && (rc = recover ? bcp_pq_recover_stripes_async(L->qk, pl->st2, ns2, pl->so2, nsrc2, pl->lost)
+                                  : bcp_pq_stripes_async(L->qk, pl->st2, ns2, pl->so2, nsrc2, pl->qd))) ||
             (rc = bcp_event_record(S->ev_k, L->qk)) ||
             (rc = bcp_queue_wait_event(L->qd, S->ev_k)) ||
             (rc = bcp_d2h_async(L->qd, S->h_out, S->d_out, (size_t)out_used)) ||
@@ -1334,13 +1547,16 @@ static int pipeline_exec(bcp_pipeline *pl, const char *store_root, task *tasks, 
             break;
         /* writes start once the batch's D2H is done (completion thread); the
          * host moves on to batch b+1 meanwhile */
-        latch_init(&S->writes, (long)(last - first));
+        latch_init(&S->writes, verify ? (long)(last - first) : nwrites);
         S->busy = 1;
         complete_arg *ca = &cargs[b];
         *ca = (complete_arg){{0}, S, store_root, tasks, wa, first, last, &pl->io, log, &errors, &dev_rc};
         pool_push(&pl->completer, &ca->j, do_complete);
         for (size_t i = first; i < last && !verify; i++)
-            bytes_written += (tasks[i].rebuild ? 0 : 8u * (uint64_t)tasks[i].n) + tasks[i].out_len;
+            bytes_written += (tasks[i].rebuild ? 0 : 8u * (uint64_t)tasks[i].n) + tasks[i].out_len +
+                             (!tasks[i].has2         ? 0
+                              : tasks[i].rebuild ? tasks[i].out_len2
+                                                 : 8u * (uint64_t)tasks[i].n + tasks[i].out_len2);
         ntasks += last - first;
         tm.submit += now_s() - ts;
     }
@@ -1449,6 +1665,7 @@ int bcp_pipeline_rebuild(bcp_pipeline *pl, const char *store_root, int ntargets,
         task *t = &tasks[nt++];
         t->path = items[i].path;
         t->p = rebuild_target;
+        t->q_st = -1;
         t->rebuild = 1;
         t->timestamp = fi->timestamp;
         /* sources: the surviving holders and the parity holder, ascending
@@ -1517,6 +1734,7 @@ int bcp_pipeline_verify(bcp_pipeline *pl, const char *store_root, int ntargets, 
         task *t = &tasks[nt++];
         t->path = items[i].path;
         t->p = P;
+        t->q_st = -1;
         t->verify = 1;
         t->item = i;
         t->timestamp = fi->timestamp;
@@ -1556,6 +1774,170 @@ out:
     free(tasks);
     if (res != results)
         free(res);
+    return rc;
+}
+
+int bcp_pipeline_set_q_parity(bcp_pipeline *pl, int on)
+{
+    if (!pl || (on != 0 && on != 1))
+        return -EINVAL;
+    pl->q_on = on;
+    return 0;
+}
+
+int bcp_pipeline_q_stats(const bcp_pipeline *pl, uint64_t *written, uint64_t *no_target, uint64_t *windowed)
+{
+    if (!pl)
+        return -EINVAL;
+    if (written)
+        *written = pl->q_written;
+    if (no_target)
+        *no_target = pl->q_no_target;
+    if (windowed)
+        *windowed = pl->q_windowed;
+    return 0;
+}
+
+int bcp_pipeline_rebuild2(bcp_pipeline *pl, const char *store_root, int ntargets, int target_a, int target_b,
+                          const bcp_work_item *items, size_t nitems, const char *corrupt_list_path,
+                          const char *lost_list_path, FILE *log, bcp_run_stats *stats, bcp_rebuild2_stats *st2)
+{
+    if (!pl || !store_root || ntargets < 2 || ntargets > MAX_STORAGE_TARGETS || target_a < 0 || target_a >= ntargets ||
+        target_b < 0 || target_b >= ntargets || target_a == target_b || (nitems && !items))
+        return -EINVAL;
+    double t0 = now_s();
+    for (size_t i = 0; i < nitems; i++) {
+        uint64_t loc = items[i].fi.locations;
+        int P = GET_P(loc);
+        if ((uint64_t)P == NO_P)
+            continue;
+        if (!items[i].path || P >= ntargets || TEST_BIT(loc, P) || ((loc & L_MASK) >> ntargets))
+            return -EINVAL;
+    }
+    int corrupt_fd = -1, lost_fd = -1, rc = 0;
+    task *tasks = NULL;
+    uint8_t *unrec = NULL, *kind = NULL; /* per item: unrecoverable; 1 xor, 2 q, 3 pq task */
+    if (corrupt_list_path) {
+        corrupt_fd = open(corrupt_list_path, O_WRONLY | O_CREAT | O_TRUNC | O_APPEND, S_IRUSR | S_IWUSR);
+        if (corrupt_fd < 0)
+            return -errno;
+    }
+    if (lost_list_path) {
+        lost_fd = open(lost_list_path, O_WRONLY | O_CREAT | O_TRUNC | O_APPEND, S_IRUSR | S_IWUSR);
+        if (lost_fd < 0) {
+            rc = -errno;
+            goto out;
+        }
+    }
+    tasks = calloc(nitems ? nitems : 1, sizeof(task));
+    unrec = calloc(nitems ? nitems : 1, 1);
+    kind = calloc(nitems ? nitems : 1, 1);
+    if (!tasks || !unrec || !kind) {
+        rc = -ENOMEM;
+        goto out;
+    }
+    const uint64_t lmask = (UINT64_C(1) << target_a) | (UINT64_C(1) << target_b);
+    uint64_t refused = 0;
+    size_t nt = 0;
+    for (size_t i = 0; i < nitems; i++) {
+        const FileInfo *fi = &items[i].fi;
+        const uint64_t loc = fi->locations;
+        const int P = GET_P(loc);
+        const uint64_t lostH = loc & L_MASK & lmask;
+        /* do_file's skip rules (rebuild/main.c:48-51) for either target */
+        if ((uint64_t)P == NO_P || !lostH)
+            continue;
+        if (!bcpi_path_ok(items[i].path, (size_t)-1)) { /* as process_task: refused, skipped */
+            if (log)
+                fprintf(log, "bcp_pipeline: refusing '%s': not a path inside the store\n", items[i].path);
+            refused++;
+            continue;
+        }
+        const int two = lostH == lmask;
+        const int p_lost = P == target_a || P == target_b;
+        task *t = &tasks[nt];
+        memset(t, 0, sizeof(*t));
+        t->path = items[i].path;
+        t->item = i;
+        t->q_st = -1;
+        t->rebuild = 1;
+        t->timestamp = fi->timestamp;
+        t->parity_src = -1;
+        t->q_src = -1;
+        if (!two && !p_lost) {
+            /* one victim, P present: bcp_pipeline_rebuild's task for it */
+            const int victim = TEST_BIT(lostH, target_a) ? target_a : target_b;
+            const uint64_t src = ((loc & L_MASK) | (UINT64_C(1) << P)) & ~(UINT64_C(1) << victim);
+            t->p = victim;
+            for (int k = 0; k < MAX_STORAGE_TARGETS; k++)
+                if (TEST_BIT(src, k)) {
+                    if (k == P)
+                        t->parity_src = t->n;
+                    t->holders[t->n++] = k;
+                }
+            kind[i] = 1;
+            nt++;
+            continue;
+        }
+        /* Q is needed */
+        const int qt = bcp_q_target(loc, ntargets);
+        if (qt < 0) {
+            unrec[i] = 1;
+            continue;
+        }
+        t->pq = two ? 2 : 1;
+        int nlost = 0;
+        for (int k = 0; k < MAX_STORAGE_TARGETS; k++)
+            if (TEST_BIT(loc & L_MASK, k)) {
+                if (TEST_BIT(lostH, k)) {
+                    if (nlost == 0)
+                        t->p = k;
+                    else
+                        t->p2 = k;
+                    t->lost_pos[nlost++] = t->width;
+                } else {
+                    t->src_pos[t->n] = t->width;
+                    t->holders[t->n++] = k;
+                }
+                t->width++;
+            }
+        if (two) {
+            t->parity_src = t->n;
+            t->holders[t->n++] = P;
+        }
+        t->q_src = t->n;
+        t->holders[t->n++] = qt;
+        kind[i] = two ? 3 : 2;
+        nt++;
+    }
+    pl->r2_unrec = unrec;
+    rc = pipeline_exec(pl, store_root, tasks, nt, corrupt_fd, log, stats, t0, NULL);
+    pl->r2_unrec = NULL;
+    bcp_rebuild2_stats r2 = {0, 0, 0, 0};
+    for (size_t i = 0; i < nitems; i++) {
+        if (unrec[i]) {
+            r2.unrecoverable++;
+            push_corrupt(lost_fd, items[i].path); /* (the same one-line-per-path format) */
+        } else if (kind[i] == 1) {
+            r2.xor_items++;
+        } else if (kind[i] == 2) {
+            r2.q_items++;
+        } else if (kind[i] == 3) {
+            r2.pq_items++;
+        }
+    }
+    if (st2)
+        *st2 = r2;
+    if (stats)
+        stats->refused = refused;
+out:
+    free(tasks);
+    free(unrec);
+    free(kind);
+    if (corrupt_fd >= 0)
+        close(corrupt_fd);
+    if (lost_fd >= 0)
+        close(lost_fd);
     return rc;
 }
 

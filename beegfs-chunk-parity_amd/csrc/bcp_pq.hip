@@ -1,0 +1,235 @@
+// bcp_pq.hip -- P + Q parity over GF(2^8) for gfx950.
+//
+// Field: polynomial x^8+x^4+x^3+x^2+1 (0x11d), generator g = 2 (the RAID-6
+// convention).  For a stripe of sources D_0 .. D_{n-1} in position order,
+// each zero-padded to out_len:
+//   P[j] = XOR_k D_k[j]            Q[j] = XOR_k g^k * D_k[j]
+// Q is evaluated in Horner form, q = 0; for k = n-1 .. 0: q = 2*q ^ D_k, on
+// four packed bytes of a dword at a time (mul2): no multiply, no table, no
+// LDS.  One pass over the sources yields both.
+//
+// Two forms of that pass:
+//   GEN    the epilogue stores Q, and P when the stripe has a P address;
+//   SOLVE  the sources are the survivors (lost positions have len 0 and
+//          contribute 2*q steps only), the P and Q bodies are loaded with the
+//          first sources and XORed in, which makes the accumulators the
+//          syndromes Ps and Qs; the epilogue stores D_x = ca*Ps ^ cb*Qs and
+//          D_y = Ps ^ D_x, each truncated to its own length.  ca, cb are
+//          per-stripe constants from the host (P lost: ca = 0, cb = g^-x).
+//
+// Schedule and load shape are the descriptor fold's (bcp_kernels.hip): a
+// device-wide atomicAdd-fed tile queue, wave-contiguous lanes, 16-byte
+// non-temporal loads, every load of a group of four sources issued before its
+// arithmetic.  Per tile and per source the coverage test is wave-uniform: a
+// source covers the tile, misses it (a 2*q step without a load) or ends inside
+// it (per-lane tail loads).  The runs keep the caller's order -- the position
+// is the coefficient -- so the tile records are the host's (PqTile), not
+// desc_tiles'.
+#include "bcp_kernel_util.h"
+
+namespace bcp {
+
+// 2*x on four packed field elements.
+__device__ __forceinline__ v4u mul2(v4u x) {
+  const v4u m = x & 0x80808080u;
+  return ((x << 1) & 0xfefefefeu) ^ (((m << 1) - (m >> 7)) & 0x1d1d1d1du);
+}
+
+// G consecutive sources run[0 .. G) of a stripe, folded highest position
+// first: q = 2*q ^ D, p ^= D.  Every load of the group goes out before the
+// arithmetic.
+template <int G, int U>
+__device__ __forceinline__ void pq_group(v4u (&p)[U], v4u (&q)[U], const_as<bcp_source> *run, uint64_t off,
+                                         uint32_t T, uint32_t lane_off) {
+  uint64_t ptr[G], len[G];
+  bool cover = true;
+#pragma unroll
+  for (int i = 0; i < G; i++) {
+    ptr[i] = run[i].ptr;
+    len[i] = run[i].len;
+    cover = cover && len[i] >= off + T;
+  }
+  v4u x[G][U];
+  if (cover) {
+#pragma unroll
+    for (int i = 0; i < G; i++) {
+      const glob<v4u_u> *s = gp<const v4u_u>(ptr[i] + off + lane_off);
+#pragma unroll
+      for (int u = 0; u < U; u++) x[i][u] = __builtin_nontemporal_load(s + u * 64);
+    }
+  } else {
+#pragma unroll
+    for (int i = 0; i < G; i++) {
+      if (len[i] >= off + T) {
+        const glob<v4u_u> *s = gp<const v4u_u>(ptr[i] + off + lane_off);
+#pragma unroll
+        for (int u = 0; u < U; u++) x[i][u] = __builtin_nontemporal_load(s + u * 64);
+      } else if (len[i] <= off) {  // zero padding (also a (0, 0) source: never dereferenced)
+#pragma unroll
+        for (int u = 0; u < U; u++) x[i][u] = zero4();  // (never read: the 2*q step below)
+      } else {
+        gbyte *s = gp<const unsigned char>(ptr[i] + off);
+        const uint64_t left = len[i] - off;  // < T: the source ends inside the tile
+#pragma unroll
+        for (int u = 0; u < U; u++) x[i][u] = load_src_tail(s, left, lane_off + u * 1024u);
+      }
+    }
+    // a source that misses the tile is a 2*q step only (uniform branch)
+#pragma unroll
+    for (int i = G - 1; i >= 0; i--) {
+      if (len[i] <= off) {
+#pragma unroll
+        for (int u = 0; u < U; u++) q[u] = mul2(q[u]);
+      } else {
+#pragma unroll
+        for (int u = 0; u < U; u++) {
+          q[u] = mul2(q[u]) ^ x[i][u];
+          p[u] ^= x[i][u];
+        }
+      }
+    }
+    return;
+  }
+#pragma unroll
+  for (int i = G - 1; i >= 0; i--)
+#pragma unroll
+    for (int u = 0; u < U; u++) {
+      q[u] = mul2(q[u]) ^ x[i][u];
+      p[u] ^= x[i][u];
+    }
+}
+
+// r = c * x for a wave-uniform constant c: shift-and-add over the bits of c.
+template <int U>
+__device__ __forceinline__ void mulc_acc(v4u (&r)[U], const v4u (&x0)[U], uint32_t c) {
+  v4u x[U];
+#pragma unroll
+  for (int u = 0; u < U; u++) x[u] = x0[u];
+#pragma unroll
+  for (int bit = 0; bit < 8; bit++) {
+    if (c & (1u << bit)) {
+#pragma unroll
+      for (int u = 0; u < U; u++) r[u] ^= x[u];
+    }
+    if (bit < 7 && (c >> (bit + 1)) != 0) {
+#pragma unroll
+      for (int u = 0; u < U; u++) x[u] = mul2(x[u]);
+    }
+  }
+}
+
+// U vectors of this lane to d[0 .. left), tile-relative.
+template <int U>
+__device__ __forceinline__ void pq_store(uint64_t d, uint64_t left, uint32_t T, uint32_t lane_off, const v4u (&v)[U]) {
+  if (left >= T) {
+    glob<v4u_u> *o = gp<v4u_u>(d + lane_off);
+#pragma unroll
+    for (int u = 0; u < U; u++) __builtin_nontemporal_store(v[u], o + u * 64);
+  } else {
+    glob<unsigned char> *o = gp<unsigned char>(d);
+#pragma unroll
+    for (int u = 0; u < U; u++) store_tail(o, left, lane_off + u * 1024u, v[u]);
+  }
+}
+
+template <int U, bool SOLVE>
+__device__ __forceinline__ void pq_tile(const PqBatch &b, uint32_t t) {
+  constexpr uint32_t T = (uint32_t)kBlock * U * 16u;
+  const_as<PqTile> *tr = cst(b.tiles) + t;
+  const_as<PqStripe> *d = cst(b.stripes) + tr->stripe;
+  const uint64_t off = (uint64_t)tr->sub * T;
+  const_as<bcp_source> *run = cst(b.sources) + d->first_src;
+  // this lane's vector u = 0 inside the tile; vector u is at + u * 1024
+  const uint32_t lane_off = ((threadIdx.x >> 6) * (64u * U) + (threadIdx.x & 63u)) * 16u;
+  const uint64_t out_left = d->out_len - off;  // > 0: the host cuts tiles below out_len only
+  v4u p[U], q[U], qb[U];
+#pragma unroll
+  for (int u = 0; u < U; u++) p[u] = q[u] = qb[u] = zero4();
+  if constexpr (SOLVE) {
+    // the P and Q bodies: p starts as P, the Q body joins after the Horner pass
+    const uint64_t pp = d->p;
+    if (out_left >= T) {
+      const glob<v4u_u> *s = gp<const v4u_u>(d->q + off + lane_off);
+#pragma unroll
+      for (int u = 0; u < U; u++) qb[u] = __builtin_nontemporal_load(s + u * 64);
+      if (pp) {
+        const glob<v4u_u> *s2 = gp<const v4u_u>(pp + off + lane_off);
+#pragma unroll
+        for (int u = 0; u < U; u++) p[u] = __builtin_nontemporal_load(s2 + u * 64);
+      }
+    } else {
+      gbyte *s = gp<const unsigned char>(d->q + off);
+#pragma unroll
+      for (int u = 0; u < U; u++) qb[u] = load_src_tail(s, out_left, lane_off + u * 1024u);
+      if (pp) {
+        gbyte *s2 = gp<const unsigned char>(pp + off);
+#pragma unroll
+        for (int u = 0; u < U; u++) p[u] = load_src_tail(s2, out_left, lane_off + u * 1024u);
+      }
+    }
+  }
+  uint32_t k = d->nsrc;
+  // the highest positions that miss the tile: q is still zero there, nothing to do
+  while (k > 0 && run[k - 1].len <= off) k--;
+  while (k >= 4) {
+    k -= 4;
+    pq_group<4, U>(p, q, run + k, off, T, lane_off);
+  }
+  switch (k) {
+    case 3: pq_group<3, U>(p, q, run, off, T, lane_off); break;
+    case 2: pq_group<2, U>(p, q, run, off, T, lane_off); break;
+    case 1: pq_group<1, U>(p, q, run, off, T, lane_off); break;
+    default: break;
+  }
+  if constexpr (SOLVE) {
+#pragma unroll
+    for (int u = 0; u < U; u++) q[u] ^= qb[u];  // p = Ps, q = Qs
+    v4u dx[U];
+#pragma unroll
+    for (int u = 0; u < U; u++) dx[u] = zero4();
+    mulc_acc<U>(dx, p, d->ca);
+    mulc_acc<U>(dx, q, d->cb);
+    const uint64_t len_x = d->len_x, len_y = d->len_y;
+    if (len_x > off) pq_store<U>(d->dx + off, len_x - off, T, lane_off, dx);
+    if (len_y > off) {
+#pragma unroll
+      for (int u = 0; u < U; u++) dx[u] ^= p[u];
+      pq_store<U>(d->dy + off, len_y - off, T, lane_off, dx);
+    }
+  } else {
+    pq_store<U>(d->q + off, out_left, T, lane_off, q);
+    const uint64_t pp = d->p;
+    if (pp) pq_store<U>(pp + off, out_left, T, lane_off, p);
+  }
+}
+
+template <int U, bool SOLVE>
+__global__ __launch_bounds__(kBlock) void pq_desc(PqBatch b) {
+  // Work queue, one tile per grab (two LDS slots as in stream_body).
+  __shared__ uint32_t next[2];
+  if (threadIdx.x == 0) next[0] = queue_grab(b.ctr, b.base);
+  __syncthreads();
+  uint32_t t = __builtin_amdgcn_readfirstlane(next[0]);
+  int slot = 0;
+  while (t < b.ntiles) {
+    pq_tile<U, SOLVE>(b, t);
+    slot ^= 1;
+    if (threadIdx.x == 0) next[slot] = queue_grab(b.ctr, b.base);
+    __syncthreads();
+    t = __builtin_amdgcn_readfirstlane(next[slot]);
+  }
+}
+
+hipError_t launch_pq(hipStream_t st, int grid, int vecs, bool solve, const PqBatch &b) {
+  if (grid <= 0 || !pq_vecs_ok(vecs)) return hipErrorInvalidValue;
+  if (vecs == 8) {
+    if (solve) hipLaunchKernelGGL((pq_desc<8, true>), dim3(grid), dim3(kBlock), 0, st, b);
+    else hipLaunchKernelGGL((pq_desc<8, false>), dim3(grid), dim3(kBlock), 0, st, b);
+  } else {
+    if (solve) hipLaunchKernelGGL((pq_desc<4, true>), dim3(grid), dim3(kBlock), 0, st, b);
+    else hipLaunchKernelGGL((pq_desc<4, false>), dim3(grid), dim3(kBlock), 0, st, b);
+  }
+  return hipGetLastError();
+}
+
+}  // namespace bcp

@@ -6,7 +6,7 @@
  *   bcp find-all-chunks <chunks_dir>
  *       bp-find-all-chunks: the record stream on stdout.
  *   bcp parity-gen --complete|--partial [--pipeline|--protocol|--procs] [--fold MODE]
- *                  [--read PATH] [--lanes N] [--force] [--changelog DIR] <store_root> <ntargets>
+ *                  [--read PATH] [--lanes N] [--force] [--changelog DIR] [--q] <store_root> <ntargets>
  *       beegfs-parity-gen + bp-parity-gen (src/beegfs-parity-gen:1-135,
  *       gen/main.c): target bookkeeping, phase 1 from a scan of every
  *       target (--complete) or from record files DIR/st<k> (--partial,
@@ -26,11 +26,17 @@
  *       an existing state needs --force and first
  *       deletes the old parity data and DBs (the script's clean_old,
  *       :94-108, :120-126).  On success <root>/last-gen-timestamp.
+ *       --q (pipeline only; usage with --protocol / --procs): also write the Q
+ *       parity files <root>/st<q>/parityq/<path> (bcp_pipeline_set_q_parity).
  *   bcp parity-rebuild [--pipeline|--protocol|--procs] [--fold MODE] [--read PATH] [--lanes N]
- *                      [--db DIR] [--corrupt FILE] <store_root> <ntargets> <target>
+ *                      [--db DIR] [--corrupt FILE] [--also TARGET] [--lost FILE]
+ *                      <store_root> <ntargets> <target>
  *       beegfs-parity-rebuild + bp-parity-rebuild (rebuild/main.c), through
  *       the batched pipeline (default), the per-rank protocol (--protocol)
- *       or rank processes (--procs).
+ *       or rank processes (--procs).  --also TARGET (pipeline only): a second
+ *       target is lost too; chunks are rebuilt from P, from Q or from both
+ *       (bcp_pipeline_rebuild2), the paths that cannot be go to --lost FILE and
+ *       the exit status is then 1.
  *   bcp parity-verify [--db DIR] [--bad FILE] [--read PATH] <store_root> <ntargets>
  *       The scrub (no counterpart in the reference): for every item of the
  *       database (default <root>/st0/db) the batched pipeline reads the chunks
@@ -62,16 +68,19 @@ static int usage(void)
 {
     fputs("usage: bcp find-all-chunks <chunks_dir>\n"
           "       bcp parity-gen --complete|--partial [--pipeline|--protocol|--procs] [--fold MODE] [--read PATH]\n"
-          "                      [--lanes N] [--force] [--changelog DIR] <store_root> <ntargets>\n"
+          "                      [--lanes N] [--force] [--changelog DIR] [--q] <store_root> <ntargets>\n"
           "       bcp parity-rebuild [--pipeline|--protocol|--procs] [--fold MODE] [--read PATH] [--lanes N]\n"
-          "                          [--db DIR] [--corrupt FILE] <store_root> <ntargets> <target>\n"
+          "                          [--db DIR] [--corrupt FILE] [--also TARGET] [--lost FILE]\n"
+          "                          <store_root> <ntargets> <target>\n"
           "       bcp parity-verify [--db DIR] [--bad FILE] [--read PATH] <store_root> <ntargets>\n"
           "       engine: --pipeline (default: batched pipeline on every GPU) | --protocol (per-rank\n"
           "               process_task, ranks as threads) | --procs (ranks as processes)\n"
           "       MODE (protocol P-role fold): pipelined (default) | batched\n"
           "       PATH (pipeline read path): auto (default: copy in memory, direct for cold disk stores) | copy |\n"
           "            direct (O_DIRECT)\n"
-          "       --read applies to the pipeline only, --fold to --protocol / --procs only\n",
+          "       --read applies to the pipeline only, --fold to --protocol / --procs only\n"
+          "       --q (also write Q parity files) and --also TARGET (a second lost target; --lost FILE lists\n"
+          "            what cannot be rebuilt) apply to the pipeline only\n",
           stderr);
     return 1;
 }
@@ -183,6 +192,7 @@ static int cmd_gen(int argc, char **argv)
 {
     const double t_start = now_s();
     int complete = -1, engines = 0, use_pipeline = 1, use_procs = 0, lanes = 12, force = 0, read_arg = 0, fold_arg = 0;
+    int q_parity = 0;
     const char *changelog = NULL;
     int i = 0;
     for (; i < argc && argv[i][0] == '-'; i++) {
@@ -208,6 +218,8 @@ static int cmd_gen(int argc, char **argv)
         }
         else if (!strcmp(argv[i], "--force"))
             force = 1;
+        else if (!strcmp(argv[i], "--q"))
+            q_parity = 1;
         else if (!strcmp(argv[i], "--lanes") && i + 1 < argc)
             lanes = atoi(argv[++i]);
         else if (!strcmp(argv[i], "--changelog") && i + 1 < argc)
@@ -215,7 +227,8 @@ static int cmd_gen(int argc, char **argv)
         else
             return usage();
     }
-    if (complete < 0 || argc - i != 2 || engines > 1 || (read_arg && !use_pipeline) || (fold_arg && use_pipeline))
+    if (complete < 0 || argc - i != 2 || engines > 1 || (read_arg && !use_pipeline) || (fold_arg && use_pipeline) ||
+        (q_parity && !use_pipeline))
         return usage();
     const char *root = argv[i];
     const int ntargets = atoi(argv[i + 1]);
@@ -236,6 +249,9 @@ static int cmd_gen(int argc, char **argv)
         }
         for (int k = 0; k < ntargets; k++) {
             snprintf(p, sizeof(p), "%s/st%d/parity", root, k);
+            if ((rc = clear_dir(p)))
+                return fail("removing old parity data", rc);
+            snprintf(p, sizeof(p), "%s/st%d/parityq", root, k);
             if ((rc = clear_dir(p)))
                 return fail("removing old parity data", rc);
             snprintf(p, sizeof(p), "%s/st%d/db", root, k);
@@ -278,6 +294,8 @@ static int cmd_gen(int argc, char **argv)
         bcp_pipeline *pl = NULL;
         rc = pipeline_on_all_gpus(&pl, job_bytes_of(es, complete == 1));
         t_setup = now_s();
+        if (!rc && q_parity)
+            rc = bcp_pipeline_set_q_parity(pl, 1);
         if (!rc)
             rc = bcp_gen_round_pipeline(pl, root, ntargets, es, NULL, stderr, &st, &planned);
         if (pl)
@@ -316,15 +334,23 @@ static int cmd_gen(int argc, char **argv)
 
 static int cmd_rebuild(int argc, char **argv)
 {
-    const char *db = NULL, *corrupt = NULL;
-    int engines = 0, use_pipeline = 1, use_procs = 0, read_arg = 0, fold_arg = 0;
+    const char *db = NULL, *corrupt = NULL, *lost = NULL;
+    int engines = 0, use_pipeline = 1, use_procs = 0, read_arg = 0, fold_arg = 0, also = -1, also_arg = 0;
     int i = 0;
     for (; i < argc && argv[i][0] == '-'; i++) {
         if (!strcmp(argv[i], "--db") && i + 1 < argc)
             db = argv[++i];
         else if (!strcmp(argv[i], "--corrupt") && i + 1 < argc)
             corrupt = argv[++i];
-        else if (!strcmp(argv[i], "--pipeline"))
+        else if (!strcmp(argv[i], "--lost") && i + 1 < argc)
+            lost = argv[++i];
+        else if (!strcmp(argv[i], "--also") && i + 1 < argc) {
+            char *end = NULL;
+            also = (int)strtol(argv[++i], &end, 10);
+            if (!*argv[i] || *end || also < 0)
+                return usage();
+            also_arg = 1;
+        } else if (!strcmp(argv[i], "--pipeline"))
             engines++, use_pipeline = 1;
         else if (!strcmp(argv[i], "--protocol"))
             engines++, use_pipeline = 0;
@@ -348,13 +374,20 @@ static int cmd_rebuild(int argc, char **argv)
         return usage();
     const char *root = argv[i];
     const int ntargets = atoi(argv[i + 1]), target = atoi(argv[i + 2]);
+    if ((also_arg || lost) && (!use_pipeline || !also_arg || also == target || also >= ntargets))
+        return usage();
     bcp_run_stats st;
+    bcp_rebuild2_stats st2;
     memset(&st, 0, sizeof(st));
+    memset(&st2, 0, sizeof(st2));
     int rc;
     if (use_pipeline || use_procs) {
         char dp[4096];
         if (!db) {
-            snprintf(dp, sizeof(dp), "%s/st%d/db", root, target == 0 ? 1 : 0);
+            int from = 0; /* the first target that is not lost */
+            while (from == target || from == also)
+                from++;
+            snprintf(dp, sizeof(dp), "%s/st%d/db", root, from);
             db = dp;
         }
         struct stat sb;
@@ -374,7 +407,9 @@ static int cmd_rebuild(int argc, char **argv)
             bcp_pipeline *pl = NULL;
             rc = pipeline_on_all_gpus(&pl, 0);
             if (!rc)
-                rc = bcp_pipeline_rebuild(pl, root, ntargets, target, items, n, corrupt, stderr, &st);
+                rc = also_arg ? bcp_pipeline_rebuild2(pl, root, ntargets, target, also, items, n, corrupt, lost, stderr,
+                                                      &st, &st2)
+                              : bcp_pipeline_rebuild(pl, root, ntargets, target, items, n, corrupt, stderr, &st);
             if (pl)
                 bcp_pipeline_destroy(pl);
         }
@@ -390,7 +425,11 @@ static int cmd_rebuild(int argc, char **argv)
            target, (unsigned long long)st.tasks, st.seconds, st.bytes_read / 1048576.0,
            st.bytes_written / 1048576.0, st.errors, (unsigned long long)st.refused,
            use_pipeline ? "pipeline" : use_procs ? "rank processes" : "protocol");
-    return (st.errors || st.refused) ? 1 : 0;
+    if (also_arg)
+        printf("also target %d: %llu items from P, %llu from Q, %llu from P and Q, %llu unrecoverable\n", also,
+               (unsigned long long)st2.xor_items, (unsigned long long)st2.q_items, (unsigned long long)st2.pq_items,
+               (unsigned long long)st2.unrecoverable);
+    return (st.errors || st.refused || st2.unrecoverable) ? 1 : 0;
 }
 
 static int cmd_verify(int argc, char **argv)

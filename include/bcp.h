@@ -47,7 +47,9 @@ extern "C" {
  * through it (bcp_task.h, bcp_task_set_fold_ring) added.  Later additions
  * under 4 (nothing existing changed): the parity scrub's
  * bcp_check_stripes_async / bcp_check_result, and the "last_desc_form"
- * value 3.
+ * value 3; Q parity's bcp_pq_stripes_async / bcp_pq_recover_stripes_async /
+ * bcp_pq_lost / bcp_q_target, the "last_desc_form" values 4 and 5 and the
+ * option "pq_blocks_per_cu".
  * 3 (r05): the pipeline's MAP read mode (BCP_READ_MAP), its
  * bcp_pipeline_timing fields and bcp_host_register_dma_src removed.
  * 2 (r04): bcp_task.h's bcp_run_stats gained `refused`, bcp_pipeline_opts
@@ -184,6 +186,43 @@ int bcp_check_stripes_async(bcp_queue *q, const bcp_stripe *stripes,
                             uint32_t nstripes, const bcp_source *sources,
                             uint32_t nsources, bcp_check_result *results_dev);
 
+/* ---- P + Q parity over GF(2^8) ----------------------------------------- */
+/* Field: polynomial x^8+x^4+x^3+x^2+1 (0x11d), generator g = 2 (the RAID-6
+ * convention of Linux md).  For a stripe of nsrc sources in position order
+ * k = 0 .. nsrc-1, each zero-padded to out_len as above:
+ *   P[j] = XOR_k D_k[j]        Q[j] = XOR_k g^k * D_k[j]      0 <= j < out_len
+ * There is no window replay here (a replayed P is not the plain XOR, which
+ * the two-loss algebra needs): window != 0 is -EINVAL. */
+/* P and Q of every stripe.  stripes[s].dst = P body (0: P is not written),
+ * q_dst[s] = Q body (required); both out_len bytes.  Source k of the stripe's
+ * run has coefficient g^k (position order is kept); window must be 0. */
+int bcp_pq_stripes_async(bcp_queue *q, const bcp_stripe *stripes, uint32_t nstripes,
+                         const bcp_source *sources, uint32_t nsources, const uint64_t *q_dst);
+
+#define BCP_PQ_NONE 0xFFFFFFFFu
+typedef struct bcp_pq_lost {
+    uint64_t p;            /* P body, out_len readable bytes; 0: P is lost too (then y must be NONE) */
+    uint64_t q;            /* Q body, out_len readable bytes; required */
+    uint32_t x, y;         /* lost positions, x < y < nsrc; y = BCP_PQ_NONE: only x */
+    uint64_t dst_x, len_x; /* first len_x (<= out_len) bytes of member x are written */
+    uint64_t dst_y, len_y;
+} bcp_pq_lost;
+/* Recover up to two lost members of every stripe from the survivors and the
+ * parities: two data members from P and Q, or one data member from Q alone
+ * when P is lost too.  stripes[s]: the survivors in position order, lost
+ * positions with len 0; dst is ignored.  (p != 0 with y = NONE is plain
+ * RAID-5: -EINVAL, use bcp_xor_stripes_async.)  -EINVAL also for a lost
+ * position whose source has len != 0 and for len_x or len_y above out_len. */
+int bcp_pq_recover_stripes_async(bcp_queue *q, const bcp_stripe *stripes, uint32_t nstripes,
+                                 const bcp_source *sources, uint32_t nsources, const bcp_pq_lost *lost);
+/* Storage target of an item's Q file (pure host arithmetic, no device):
+ * `locations` as in bcp_task.h's FileInfo (bits 0..55 chunk holders, bits
+ * 56..63 the parity target P).  The first of P+1, P+2, ... (mod ntargets)
+ * that is neither a holder nor P; -1 when there is none, when the item has no
+ * valid P (NO_P, P a holder, P >= ntargets) and for ntargets outside
+ * 1..BCP_MAX_SOURCES. */
+int bcp_q_target(uint64_t locations, int ntargets);
+
 /* ---- resident fold ring ------------------------------------------------ */
 /* One kernel launch that stays on the device and folds stripes published
  * into a ring of descriptors in pinned host memory: no launch and no stream
@@ -273,6 +312,9 @@ int bcp_set_tuning(bcp_engine *eng, int blocks_per_cu, int vecs_per_thread);
  *   default 131072), "desc_reuse_records" (1: a batch resubmitted on a ring
  *   slot with byte-identical staged tables reuses that slot's tile records;
  *   default 0, an A/B knob);
+ *  P + Q kernel (bcp_pq_*): tiles of "desc_vecs_per_thread" vectors per lane
+ *   where that is 4 or 8 (else by batch size), "pq_blocks_per_cu" workgroups
+ *   per CU (1..8, default 2), or "desc_grid" workgroups when that is set;
  *  resident fold ring: "ring_spin_us" (a waiter spins this long, default 4)
  *   and "ring_sleep_us" (then sleeps this long between looks, default 10;
  *   0 = sched_yield instead);
@@ -290,7 +332,8 @@ int bcp_set_option(bcp_engine *eng, const char *key, int value);
  * launch: "last_stream_vecs" (vecs_per_thread of the streaming kernel),
  * "last_desc_vecs" and "last_desc_form" (descriptor kernel: 1 = desc_tiles +
  * xor_desc, 2 = xor_desc_args, 3 = desc_tiles + the check kernel of
- * bcp_check_stripes_async). */
+ * bcp_check_stripes_async, 4 = the P + Q kernel of bcp_pq_stripes_async,
+ * 5 = its recovery form, bcp_pq_recover_stripes_async). */
 int bcp_get_option(bcp_engine *eng, const char *key, int *value);
 /* Timer slots for bcp_queue_mark / bcp_queue_elapsed_ms. */
 #define BCP_TIMER_SLOTS 64

@@ -684,6 +684,42 @@ typedef struct {
 int bcp_pipeline_verify(bcp_pipeline *pl, const char *store_root, int ntargets, const bcp_work_item *items,
                         size_t nitems, bcp_verify_item *results, const char *bad_list_path, FILE *log,
                         bcp_verify_stats *stats);
+/* ---- Q parity (a second, Reed-Solomon parity per item; added under ABI 4) --
+ * With Q on, bcp_pipeline_run and bcp_gen_round_pipeline also write, per item,
+ *   <root>/st<q>/parityq/<path>,  q = bcp_q_target(locations, ntargets):
+ * the same n x u64 sizes header as the parity file, then max_cs bytes of
+ * Q = XOR_j g^j * chunk_j over GF(2^8) (bcp.h), where the j-th holder in
+ * ascending target order has position j.  P files are byte-identical to a run
+ * without Q.  An item gets no Q file when it has no Q target (every target is
+ * a holder or P) or when max_cs > BCP_WINDOW_BYTES (windowed items: their P is
+ * the reference's replayed stream, not the plain XOR); it is then protected by
+ * P only, and a Q file found at its Q target is unlinked.  An item without
+ * holders unlinks both files.  Failed Q writes count in `errors`.  When an
+ * item's holders change, its Q target may move: the old Q file is never read
+ * again but is not removed.  Default 0: everything as without this call. */
+int bcp_pipeline_set_q_parity(bcp_pipeline *pl, int on);
+/* Of the last run: Q files written, items left without one for lack of a Q
+ * target, and windowed items.  Each pointer may be NULL. */
+int bcp_pipeline_q_stats(const bcp_pipeline *pl, uint64_t *written, uint64_t *no_target, uint64_t *windowed);
+/* Rebuild of two lost targets.  Per item, with H its holders:
+ *   no holder lost           skipped (lost parity files are not rewritten: a
+ *                            later gen writes them, as do_file's rule for P)
+ *   one lost, P not lost     exactly bcp_pipeline_rebuild for that item and
+ *                            target                              (xor_items)
+ *   one lost, P lost too     recovered from Q                    (q_items)
+ *   two lost                 recovered from P and Q, each chunk truncated to
+ *                            its header size                     (pq_items)
+ * A needed P or Q file is usable when it exists with size 8n + max(header);
+ * when both are used their headers must be equal.  An item that needs Q but
+ * has none, whose needed file is not usable, or that is windowed and needs Q
+ * is unrecoverable: nothing is written for it, its path goes to the lost list
+ * (created and truncated like the corrupt list; item order), the run goes on
+ * and returns 0.  Validation as bcp_pipeline_rebuild, and target_a !=
+ * target_b.  stats and st2 may be NULL. */
+typedef struct { uint64_t xor_items, q_items, pq_items, unrecoverable; } bcp_rebuild2_stats;
+int bcp_pipeline_rebuild2(bcp_pipeline *pl, const char *store_root, int ntargets, int target_a, int target_b,
+                          const bcp_work_item *items, size_t nitems, const char *corrupt_list_path,
+                          const char *lost_list_path, FILE *log, bcp_run_stats *stats, bcp_rebuild2_stats *st2);
 /* bcp_gen_round with the batched pipeline as the engine; the replicas are
  * updated after the run, only when it finished without errors. */
 int bcp_gen_round_pipeline(bcp_pipeline *pl, const char *store_root, int ntargets, const bcp_eventset *events,

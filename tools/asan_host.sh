@@ -9,7 +9,7 @@ R=$(cd "$(dirname "$0")/.." && pwd)
 P=$R/beegfs-chunk-parity_amd
 B=$P/build-asan
 mkdir -p $B
-make -s -C $P build/bcp_kernels.o build/bcp_engine.o
+make -s -C $P build/bcp_kernels.o build/bcp_pq.o build/bcp_engine.o
 CF="-std=gnu11 -O1 -g -fPIC -Wall -pthread -fsanitize=address,undefined -fno-omit-frame-pointer -fno-sanitize-recover=undefined -I$R/include -I$P/csrc"
 objs=""
 for c in $P/csrc/*.c; do
@@ -18,7 +18,7 @@ for c in $P/csrc/*.c; do
   gcc $CF -c $c -o $B/$n.o
   objs="$objs $B/$n.o"
 done
-gcc -shared -fsanitize=address,undefined -o $B/libbcp_asan.so $objs $P/build/bcp_kernels.o $P/build/bcp_engine.o \
+gcc -shared -fsanitize=address,undefined -o $B/libbcp_asan.so $objs $P/build/bcp_kernels.o $P/build/bcp_pq.o $P/build/bcp_engine.o \
   -Wl,--version-script=$P/csrc/libbcp.map -L/opt/rocm/lib -lamdhip64 -Wl,-rpath,/opt/rocm/lib -lstdc++ -pthread
 ASAN_LIB=$(gcc -print-file-name=libasan.so)
 UBSAN_LIB=$(gcc -print-file-name=libubsan.so)

@@ -14,5 +14,5 @@ for c in "$P"/csrc/*.c; do
 done
 gcc -O2 -fPIC -pthread -c "$R/tools/exp/lockstat/lockstat.c" -o "$O/build/lockstat.o"
 /opt/rocm/bin/hipcc --offload-arch=gfx950 -shared -fPIC -o "$O/lib/libbcp.so" "$O"/build/*.o \
-    "$P/build/bcp_kernels.o" "$P/build/bcp_engine.o" -lpthread
+    "$P/build/bcp_kernels.o" "$P/build/bcp_pq.o" "$P/build/bcp_engine.o" -lpthread
 echo "$O/lib/libbcp.so"

@@ -10,7 +10,7 @@ R=$(cd "$(dirname "$0")/.." && pwd)
 P=$R/beegfs-chunk-parity_amd
 B=$P/build-tsan
 mkdir -p $B
-make -s -C $P build/bcp_kernels.o build/bcp_engine.o
+make -s -C $P build/bcp_kernels.o build/bcp_pq.o build/bcp_engine.o
 CF="-std=gnu11 -O1 -g -fPIC -Wall -pthread -fsanitize=thread -fno-omit-frame-pointer -I$R/include -I$P/csrc"
 objs=""
 for c in $P/csrc/*.c; do
@@ -21,7 +21,7 @@ for c in $P/csrc/*.c; do
 done
 gcc $CF -c $R/tests/native/protocol_driver.c -o $B/driver.o
 gcc $CF -c $R/tests/native/cpu_xor_hook.c -o $B/hook.o
-gcc -fsanitize=thread -o $B/protocol_driver $B/driver.o $B/hook.o $objs $P/build/bcp_kernels.o $P/build/bcp_engine.o \
+gcc -fsanitize=thread -o $B/protocol_driver $B/driver.o $B/hook.o $objs $P/build/bcp_kernels.o $P/build/bcp_pq.o $P/build/bcp_engine.o \
   -L/opt/rocm/lib -lamdhip64 -Wl,-rpath,/opt/rocm/lib -lstdc++ -lm -pthread
 rm -rf /tmp/bcp_tsan_store
 TSAN_OPTIONS="halt_on_error=1 second_deadlock_stack=1" $B/protocol_driver /tmp/bcp_tsan_store
@@ -33,7 +33,7 @@ rm -rf /tmp/bcp_tsan_store
 # process per target on the socketpair transport; 3 lanes per rank share
 # that rank's sockets (progress by the waiting threads, unexpected messages)
 gcc $CF -c $R/tests/native/caller_test.c -o $B/caller.o
-gcc -fsanitize=thread -o $B/caller_test $B/caller.o $objs $P/build/bcp_kernels.o $P/build/bcp_engine.o \
+gcc -fsanitize=thread -o $B/caller_test $B/caller.o $objs $P/build/bcp_kernels.o $P/build/bcp_pq.o $P/build/bcp_engine.o \
   -L/opt/rocm/lib -lamdhip64 -Wl,-rpath,/opt/rocm/lib -lstdc++ -lm -pthread
 rm -rf /tmp/bcp_tsan_caller
 TSAN_OPTIONS="halt_on_error=1 second_deadlock_stack=1" $B/caller_test /tmp/bcp_tsan_caller

@@ -21,14 +21,14 @@ if [ "$SAN" = address ]; then
   CC=gcc
   FS="-fsanitize=address,undefined -fno-sanitize-recover=undefined"
   LD="gcc $FS"
-  HIPOBJS="$P/build/bcp_kernels.o $P/build/bcp_engine.o"
+  HIPOBJS="$P/build/bcp_kernels.o $P/build/bcp_pq.o $P/build/bcp_engine.o"
 else
   CC=$ROCM/lib/llvm/bin/clang
   FS="-fsanitize=thread"
   LD="$ROCM/lib/llvm/bin/clang++ $FS"
   HF="--offload-arch=gfx950 -O1 -g -fPIC -std=c++17 -Wall -I$R/include -I$P/csrc"
   $ROCM/bin/hipcc $HF -Xarch_host -fsanitize=thread -Xarch_host -fno-omit-frame-pointer -c $P/csrc/bcp_engine.hip -o $B/bcp_engine.o
-  HIPOBJS="$P/build/bcp_kernels.o $B/bcp_engine.o"
+  HIPOBJS="$P/build/bcp_kernels.o $P/build/bcp_pq.o $B/bcp_engine.o"
 fi
 CF="-std=gnu11 -O1 -g -fPIC -Wall -pthread $FS -fno-omit-frame-pointer -I$R/include -I$P/csrc"
 objs=""
