@@ -47,6 +47,17 @@ class PqLost(ctypes.Structure):
 PQ_NONE = 0xFFFFFFFF  # PqLost.y: only x is lost
 
 
+class PqCheckResult(ctypes.Structure):
+    """bcp_pq_check_result: one record per stripe of a syndrome check (bcp_pq_check_stripes_async)."""
+    _fields_ = [("first_bad", ctypes.c_uint64), ("p_bad", ctypes.c_uint64), ("q_bad", ctypes.c_uint64),
+                ("members", ctypes.c_uint64)]
+
+
+PQ_BAD_P, PQ_BAD_Q, PQ_BAD_NOWHERE = 1 << 56, 1 << 57, 1 << 58  # PqCheckResult.members beside bits 0..55
+PQ_CHECK_CLEAN = (2 ** 64 - 1, 0, 0, 0)  # a stripe whose P and Q bodies hold
+CULPRIT_NONE, CULPRIT_DATA, CULPRIT_P, CULPRIT_Q, CULPRIT_MANY = range(5)
+
+
 class Rebuild2Stats(ctypes.Structure):
     _fields_ = [("xor_items", ctypes.c_uint64), ("q_items", ctypes.c_uint64), ("pq_items", ctypes.c_uint64),
                 ("unrecoverable", ctypes.c_uint64)]
@@ -89,6 +100,22 @@ class VerifyStats(ctypes.Structure):
 
 
 VERIFY_OK, VERIFY_STALE, VERIFY_NO_PARITY, VERIFY_SIZE, VERIFY_MISMATCH, VERIFY_SKIPPED = range(6)
+
+
+class VerifyQItem(ctypes.Structure):
+    """bcp_verify_q_item: the Q-aware scrub's verdict for one work item."""
+    _fields_ = [("status", ctypes.c_uint32), ("q_state", ctypes.c_uint32), ("culprit", ctypes.c_uint32),
+                ("target", ctypes.c_int32), ("first_bad", ctypes.c_uint64), ("p_bad", ctypes.c_uint64),
+                ("q_bad", ctypes.c_uint64)]
+
+
+class VerifyQStats(ctypes.Structure):
+    _fields_ = [("v", VerifyStats), ("q_checked", ctypes.c_uint64), ("q_none", ctypes.c_uint64),
+                ("q_bad", ctypes.c_uint64), ("culprit_data", ctypes.c_uint64), ("culprit_p", ctypes.c_uint64),
+                ("culprit_q", ctypes.c_uint64), ("culprit_many", ctypes.c_uint64)]
+
+
+QSTATE_CHECKED, QSTATE_NONE, QSTATE_BAD = range(3)
 
 
 class PipelineOpts(ctypes.Structure):
@@ -160,6 +187,9 @@ _SIGS = {
                               ctypes.POINTER(ctypes.c_uint64)], ctypes.c_int),
     "bcp_pq_recover_stripes_async": ([_V, ctypes.POINTER(Stripe), ctypes.c_uint32, ctypes.POINTER(Source),
                                       ctypes.c_uint32, ctypes.POINTER(PqLost)], ctypes.c_int),
+    "bcp_pq_check_stripes_async": ([_V, ctypes.POINTER(Stripe), ctypes.c_uint32, ctypes.POINTER(Source),
+                                    ctypes.c_uint32, ctypes.POINTER(ctypes.c_uint64), _V], ctypes.c_int),
+    "bcp_pq_culprit": ([ctypes.POINTER(PqCheckResult), ctypes.POINTER(ctypes.c_int)], ctypes.c_int),
     "bcp_q_target": ([ctypes.c_uint64, ctypes.c_int], ctypes.c_int),
     "bcp_xor_parity": ([_V, ctypes.c_size_t, _V, ctypes.c_int], ctypes.c_int),
     "bcp_ring_create": ([_V, ctypes.c_int, ctypes.c_int, ctypes.POINTER(_V)], ctypes.c_int),
@@ -227,6 +257,9 @@ _SIGS = {
     "bcp_pipeline_verify": ([_V, ctypes.c_char_p, ctypes.c_int, ctypes.POINTER(WorkItem), ctypes.c_size_t,
                              ctypes.POINTER(VerifyItem), ctypes.c_char_p, _V, ctypes.POINTER(VerifyStats)],
                             ctypes.c_int),
+    "bcp_pipeline_verify_q": ([_V, ctypes.c_char_p, ctypes.c_int, ctypes.POINTER(WorkItem), ctypes.c_size_t,
+                               ctypes.POINTER(VerifyQItem), ctypes.c_char_p, ctypes.c_char_p, _V,
+                               ctypes.POINTER(VerifyQStats)], ctypes.c_int),
     "bcp_pipeline_set_q_parity": ([_V, ctypes.c_int], ctypes.c_int),
     "bcp_pipeline_q_stats": ([_V, ctypes.POINTER(ctypes.c_uint64), ctypes.POINTER(ctypes.c_uint64),
                               ctypes.POINTER(ctypes.c_uint64)], ctypes.c_int),
@@ -315,6 +348,17 @@ def call(fn: str, *args) -> int:
 def q_target(locations: int, ntargets: int) -> int:
     """bcp_q_target: the storage target of an item's Q file, or -1."""
     return lib().bcp_q_target(locations, ntargets)
+
+
+def pq_culprit(result) -> tuple:
+    """bcp_pq_culprit: (kind, position) -- CULPRIT_*, and the data position for CULPRIT_DATA, else -1.
+    result: a PqCheckResult or the tuple of its fields."""
+    r = result if isinstance(result, PqCheckResult) else PqCheckResult(*result)
+    pos = ctypes.c_int(-1)
+    kind = lib().bcp_pq_culprit(ctypes.byref(r), ctypes.byref(pos))
+    if kind < 0:
+        raise BcpError("bcp_pq_culprit", kind)
+    return kind, pos.value
 
 
 def device_count() -> int:
@@ -476,6 +520,14 @@ class Queue:
         so = (Source * max(len(sources), 1))(*[Source(*s) for s in sources])
         lo = (PqLost * max(len(lost), 1))(*[x if isinstance(x, PqLost) else PqLost(*x) for x in lost])
         call("bcp_pq_recover_stripes_async", self.h, st, len(stripes), so, len(sources), lo)
+
+    def pq_check(self, stripes, sources, q_body, results_ptr: int):
+        """Syndromes of every stripe: stripes as in pq_stripes but dst = P body and q_body[s] = Q body
+        are only read; results_ptr: device memory for len(stripes) PqCheckResult records."""
+        st = (Stripe * max(len(stripes), 1))(*[Stripe(*s) for s in stripes])
+        so = (Source * max(len(sources), 1))(*[Source(*s) for s in sources])
+        qb = (ctypes.c_uint64 * max(len(q_body), 1))(*q_body)
+        call("bcp_pq_check_stripes_async", self.h, st, len(stripes), so, len(sources), qb, _V(results_ptr))
 
     def fill_synthetic(self, dptr: int, nbytes: int, seed: int, byte_offset: int = 0):
         call("bcp_dev_fill_synthetic_async", self.h, _V(dptr), nbytes, seed, byte_offset)
@@ -834,6 +886,18 @@ class Pipeline:
         res = (VerifyItem * max(len(items), 1))()
         call("bcp_pipeline_verify", self.h, store_root.encode(), ntargets, arr, len(items), res,
              bad_list.encode() if bad_list else None, log, ctypes.byref(st))
+        del keep
+        return st, list(res[:len(items)])
+
+    def verify_q(self, store_root: str, ntargets: int, items, bad_list: str | None = None,
+                 culprit_list: str | None = None, log=None):
+        """bcp_pipeline_verify_q (the scrub with Q): (VerifyQStats, [VerifyQItem])."""
+        arr, keep = _items(items)
+        st = VerifyQStats()
+        res = (VerifyQItem * max(len(items), 1))()
+        call("bcp_pipeline_verify_q", self.h, store_root.encode(), ntargets, arr, len(items), res,
+             bad_list.encode() if bad_list else None, culprit_list.encode() if culprit_list else None, log,
+             ctypes.byref(st))
         del keep
         return st, list(res[:len(items)])
 

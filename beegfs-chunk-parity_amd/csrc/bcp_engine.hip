@@ -42,7 +42,7 @@ struct bcp_engine {
   pthread_mutex_t lock = PTHREAD_MUTEX_INITIALIZER;
   std::atomic<int> last_stream_vecs{0};  // U of the latest xor_stream launch (tools)
   std::atomic<int> last_desc_vecs{0};    // U of the latest descriptor-kernel launch (tools)
-  std::atomic<int> last_desc_form{0};    // 1 xor_desc (desc_tiles), 2 xor_desc_args, 3 check_desc, 4 / 5 pq_desc gen / solve
+  std::atomic<int> last_desc_form{0};    // 1 xor_desc (desc_tiles), 2 xor_desc_args, 3 check_desc, 4 / 5 / 6 pq_desc gen / solve / check
 };
 
 namespace {
@@ -1222,12 +1222,15 @@ struct Gf256 {
 const Gf256 g_gf;
 }  // namespace
 
-// Both forms: `lost` == nullptr is GEN (q_dst gives the Q bodies), else SOLVE.
+// All forms: `lost` is SOLVE; else q_dst gives the Q bodies, written (GEN) or
+// with `check` (nstripes device records, initialised on the queue first)
+// read beside the P bodies at dst (CHECK).
 // The staged tables are the stripes' records, their source runs copied in the
 // caller's order, and one record per tile; they go through stage_tables with
 // the pointer-table threshold, since the kernel reads them once per tile.
 static int submit_pq(bcp_queue *q, const bcp_stripe *stripes, uint32_t nstripes, const bcp_source *sources,
-                     uint32_t nsources, const uint64_t *q_dst, const bcp_pq_lost *lost) {
+                     uint32_t nsources, const uint64_t *q_dst, const bcp_pq_lost *lost,
+                     bcp_pq_check_result *check = nullptr) {
   bcp_engine *e = q->eng;
   uint64_t tiles8 = 0, nstaged = 0;
   for (uint32_t i = 0; i < nstripes; i++) {
@@ -1249,13 +1252,18 @@ static int submit_pq(bcp_queue *q, const bcp_stripe *stripes, uint32_t nstripes,
       if (l.len_x > s.out_len || (two && l.len_y > s.out_len)) return -EINVAL;
       if ((l.len_x && !l.dst_x) || (two && l.len_y && !l.dst_y)) return -EINVAL;
       cover = std::max(l.len_x, two ? l.len_y : (uint64_t)0);
-    } else if (s.out_len && !q_dst[i]) {
+    } else if (s.out_len && (!q_dst[i] || (check && !s.dst))) {
       return -EINVAL;
     }
     tiles8 += (cover + desc_tile_bytes(8) - 1) / desc_tile_bytes(8);
     nstaged += s.nsrc;
   }
   if (tiles8 > 0xFFFFFFF0ull / 4 || nstaged > 0xFFFFFFFFull) return -EINVAL;
+  if (check) {
+    if (q->broken) return -EIO;
+    (void)hipGetLastError();
+    HIP_RC(launch_pq_check_init(q->stream, check, nstripes));
+  }
   if (tiles8 == 0) return 0;
   int vecs = e->tuning.desc_vecs;
   // 16 KiB tiles unless asked otherwise: at 4 vectors per lane the kernel keeps three waves per
@@ -1342,10 +1350,11 @@ static int submit_pq(bcp_queue *q, const bcp_stripe *stripes, uint32_t nstripes,
   if ((uint32_t)grid > ntiles) grid = (int)ntiles;
   if (q->broken) return -EIO;
   (void)hipGetLastError();  // see launch_stream
-  const hipError_t le = launch_pq(q->stream, grid, vecs, lost != nullptr, b);
+  const hipError_t le =
+      check ? launch_pq_check(q->stream, grid, vecs, b, check) : launch_pq(q->stream, grid, vecs, lost != nullptr, b);
   if (le == hipSuccess) {
     e->last_desc_vecs.store(vecs, std::memory_order_relaxed);
-    e->last_desc_form.store(lost ? 5 : 4, std::memory_order_relaxed);
+    e->last_desc_form.store(check ? 6 : lost ? 5 : 4, std::memory_order_relaxed);
   }
   if ((rc = queue_launched(q, le, (uint64_t)ntiles + (uint64_t)grid))) return rc;
   HIP_RC(hipEventRecord(slot->done, q->stream));
@@ -1369,6 +1378,16 @@ extern "C" int bcp_pq_recover_stripes_async(bcp_queue *q, const bcp_stripe *stri
   int rc = set_device(q->eng);
   if (rc) return rc;
   return submit_pq(q, stripes, nstripes, sources, nsources, nullptr, lost);
+}
+
+extern "C" int bcp_pq_check_stripes_async(bcp_queue *q, const bcp_stripe *stripes, uint32_t nstripes,
+                                          const bcp_source *sources, uint32_t nsources, const uint64_t *q_body,
+                                          bcp_pq_check_result *results_dev) {
+  if (!q || !stripes || !q_body || !results_dev || (nsources && !sources)) return -EINVAL;
+  if (!nstripes) return 0;
+  int rc = set_device(q->eng);
+  if (rc) return rc;
+  return submit_pq(q, stripes, nstripes, sources, nsources, q_body, nullptr, results_dev);
 }
 
 extern "C" int bcp_xor_strided_async(bcp_queue *q, void *dst, uint64_t dst_stride, const void *src,

@@ -277,14 +277,15 @@ struct RingArgs {
 };
 
 // ---------------------------------------------------------------------------
-// P + Q parity (bcp_pq.hip; bcp_pq_stripes_async, bcp_pq_recover_stripes_async).
+// P + Q parity (bcp_pq.hip; bcp_pq_stripes_async, bcp_pq_recover_stripes_async,
+// bcp_pq_check_stripes_async).
 // One record per stripe and one per tile, both written by the host: the
 // sources of a run stay in the caller's position order (source k has
 // coefficient g^k), so nothing here is sorted.
 // ---------------------------------------------------------------------------
 struct alignas(16) PqStripe {
-    uint64_t p, q;          // GEN: P / Q output (p 0: no P); SOLVE: P / Q body (p 0: P is lost)
-    uint64_t out_len;       // GEN: bytes of each output; SOLVE: readable bytes of p and q
+    uint64_t p, q;          // GEN: P / Q output (p 0: no P); SOLVE: P / Q body (p 0: P is lost); CHECK: P / Q body
+    uint64_t out_len;       // GEN: bytes of each output; SOLVE, CHECK: readable bytes of p and q
     uint32_t first_src, nsrc;
     uint64_t dx, len_x;     // SOLVE: member x, its first len_x bytes
     uint64_t dy, len_y;     // SOLVE: member y (len_y 0: not asked for)
@@ -307,6 +308,11 @@ inline bool pq_vecs_ok(int v) { return v == 4 || v == 8; }
 // GEN (solve = false) or SOLVE form, vecs 4 or 8 (tile = desc_tile_bytes(vecs));
 // same work-queue accounting as launch_xor_stream (ntiles + grid).
 hipError_t launch_pq(hipStream_t st, int grid, int vecs, bool solve, const PqBatch &b);
+// CHECK form (bcp_pq_check_stripes_async): the same tiles and accounting,
+// nothing stored but res[s], the stripe's verdict.  launch_pq_check_init sets
+// n records to {UINT64_MAX, 0, 0, 0}.
+hipError_t launch_pq_check_init(hipStream_t st, bcp_pq_check_result *res, uint32_t n);
+hipError_t launch_pq_check(hipStream_t st, int grid, int vecs, const PqBatch &b, bcp_pq_check_result *res);
 
 // Kernel launchers (bcp_kernels.hip).  All return hipError_t.
 // Streaming fold.  Consumes ceil(ntiles / grab) + grid counts of a.ctr; the

@@ -37,7 +37,10 @@
  * the parity body; the device compares the fold of the chunks with the body
  * where it lies in the input slab (bcp_check_stripes_async), 16 bytes per item
  * come back in the output slab, and the completion stage turns them into
- * verdicts.  No write jobs, nothing under the store changes.
+ * verdicts.  No write jobs, nothing under the store changes.  With Q
+ * (bcp_pipeline_verify_q) an item whose Q file is in order gets one more
+ * source row, the Q body, and its stripe goes in a launch of its own per batch
+ * (bcp_pq_check_stripes_async): 32 bytes come back, the syndromes' verdict.
  *
  * Q parity (bcp_pipeline_set_q_parity, bcp_pipeline_rebuild2; bcp_task.h): a
  * task may have a second output, placed after the first in the output slab
@@ -254,6 +257,12 @@ typedef struct {
     size_t item;                         /* verify: index of the work item */
     uint32_t status;                     /* verify: BCP_VERIFY_* or VERIFY_PENDING */
     uint64_t first_bad, bad_bytes;       /* verify: the device's record */
+    /* verify with Q (bcp_pipeline_verify_q): vq = 1, q_st the item's Q target
+     * (-1: none); after the stat phase q_state, and for a CHECKED task the Q
+     * body as source q_src behind the P body */
+    int vq;
+    uint32_t q_state;
+    uint64_t q_bad, members;             /* vq, CHECKED: the rest of the record (p_bad is bad_bytes) */
     /* Q parity.  gen: q_st is the item's Q target when the run writes its Q
      * file (-1: none).  rebuild2: pq = 1 recovers the victim from Q alone (P is
      * lost too), pq = 2 both victims (p, p2) from P and Q; the sources are then
@@ -281,7 +290,7 @@ typedef struct {
 static const char *const k_dir[3] = {"chunks", "parity", "parityq"};
 static int src_kind(const task *t, int k)
 {
-    if (t->pq && k == t->q_src)
+    if ((t->pq || (t->vq && t->q_state == BCP_QSTATE_CHECKED)) && k == t->q_src)
         return 2;
     return (t->rebuild || t->verify) && k == t->parity_src;
 }
@@ -296,7 +305,7 @@ static uint64_t out_off2(const task *t)
 static uint64_t out_span(const task *t)
 {
     if (t->verify)
-        return sizeof(bcp_check_result);
+        return t->vq ? sizeof(bcp_pq_check_result) : sizeof(bcp_check_result);
     return (t->out_len + 255u) / 256u * 256u + (t->has2 ? (t->out_len2 + 255u) / 256u * 256u : 0);
 }
 
@@ -445,6 +454,33 @@ static void do_stat(job *p)
                     : !have || fsize != (uint64_t)n * 8u + t->max_cs ? BCP_VERIFY_NO_PARITY
                     : resized                                             ? BCP_VERIFY_SIZE
                                                                           : VERIFY_PENDING;
+        if (t->vq && t->status == VERIFY_PENDING) {
+            /* the Q state: by rule none, or a file in order beside P's */
+            t->q_state = BCP_QSTATE_NONE;
+            if (t->q_st >= 0 && t->max_cs <= WINDOW) {
+                uint64_t hq[MAX_STORAGE_TARGETS] = {0};
+                uint64_t qsize = 0;
+                int qhave = 0;
+                chunk_file(fn, sizeof(fn), a->root, t->q_st, "parityq", t->path);
+                fd = open(fn, O_RDONLY);
+                if (fd >= 0) {
+                    if (fstat(fd, &st) == 0)
+                        qsize = (uint64_t)st.st_size;
+                    qhave = qsize >= (uint64_t)n * 8u && pread(fd, hq, (size_t)n * 8u, 0) == (ssize_t)((size_t)n * 8u);
+                    close(fd);
+                }
+                if (qhave && qsize == (uint64_t)n * 8u + t->max_cs && memcmp(hq, header, (size_t)n * 8u) == 0) {
+                    t->q_state = BCP_QSTATE_CHECKED;
+                    t->q_src = t->n;
+                    t->holders[t->n] = t->q_st;
+                    t->src_off[t->n] = (uint64_t)n * 8u;
+                    t->size[t->n] = t->max_cs;
+                    t->n++;
+                } else {
+                    t->q_state = BCP_QSTATE_BAD;
+                }
+            }
+        }
         latch_down(a->done);
         return;
     }
@@ -749,7 +785,14 @@ static void do_complete(job *p)
         latch *done = &a.S->writes;
         for (size_t i = a.first; i < a.last; i++) {
             task *t = &a.tasks[i];
-            if (!rc) {
+            if (!rc && t->vq && t->q_state == BCP_QSTATE_CHECKED) {
+                const bcp_pq_check_result *r = (const bcp_pq_check_result *)(a.S->h_out + t->out_off);
+                t->first_bad = r->first_bad;
+                t->bad_bytes = r->p_bad;
+                t->q_bad = r->q_bad;
+                t->members = r->members;
+                t->status = r->members ? BCP_VERIFY_MISMATCH : BCP_VERIFY_OK;
+            } else if (!rc) {
                 const bcp_check_result *r = (const bcp_check_result *)(a.S->h_out + t->out_off);
                 t->first_bad = r->first_bad;
                 t->bad_bytes = r->bad_bytes;
@@ -1047,7 +1090,8 @@ fail:
 }
 
 static int pipeline_exec(bcp_pipeline *pl, const char *store_root, task *tasks, size_t nt, int corrupt_fd,
-                         FILE *log, bcp_run_stats *stats, double t0, bcp_verify_item *vres);
+                         FILE *log, bcp_run_stats *stats, double t0, bcp_verify_item *vres,
+                         bcp_verify_q_item *qres);
 
 /* Bytes source k of t takes in the input slab: its data at 256-byte pitch
  * (COPY), or the whole file prefix up to the data's end at page pitch (DIRECT:
@@ -1117,7 +1161,7 @@ int bcp_pipeline_run(bcp_pipeline *pl, const char *store_root, int ntargets, con
             if (TEST_BIT(loc, k))
                 t->holders[t->n++] = k;
     }
-    rc = pipeline_exec(pl, store_root, tasks, nt, -1, log, stats, t0, NULL);
+    rc = pipeline_exec(pl, store_root, tasks, nt, -1, log, stats, t0, NULL, NULL);
     free(tasks);
     if (stats)
         stats->refused = bcpr_count_refused(items, nitems, -1);
@@ -1209,10 +1253,12 @@ static int auto_read_mode(const char *root, const task *tasks, size_t nt, fs_kin
 }
 
 /* Stat, batch and stream the tasks through the slots (both read paths).
- * Takes no ownership of tasks.  vres: verify run (every task a verify task):
- * the verdicts of the work items, written here for every task. */
+ * Takes no ownership of tasks.  vres or qres: verify run (every task a verify
+ * task; qres: with Q, every task vq): the verdicts of the work items, written
+ * here for every task. */
 static int pipeline_exec(bcp_pipeline *pl, const char *store_root, task *tasks, size_t nt, int corrupt_fd,
-                         FILE *log, bcp_run_stats *stats, double t0, bcp_verify_item *vres)
+                         FILE *log, bcp_run_stats *stats, double t0, bcp_verify_item *vres,
+                         bcp_verify_q_item *qres)
 {
     fs_kinds fk;
     memset(&fk, -1, sizeof(fk));
@@ -1239,14 +1285,17 @@ static int pipeline_exec(bcp_pipeline *pl, const char *store_root, task *tasks, 
         latch_destroy(&l);
         free(args);
     }
-    const int verify = vres != NULL;
+    const int verify = vres != NULL || qres != NULL;
     if (verify) {
         /* only the items that passed the stat phase are read and compared:
          * the others' verdicts stand, their tasks drop out (order kept) */
         size_t w = 0;
         for (size_t i = 0; i < nt; i++) {
             if (tasks[i].status != VERIFY_PENDING) {
-                vres[tasks[i].item].status = tasks[i].status;
+                if (qres)
+                    qres[tasks[i].item].status = tasks[i].status;
+                else
+                    vres[tasks[i].item].status = tasks[i].status;
                 continue;
             }
             if (w != i)
@@ -1483,9 +1532,32 @@ static int pipeline_exec(bcp_pipeline *pl, const char *store_root, task *tasks, 
         uint64_t out_used = 0;
         long nwrites = 0;
         int recover = 0;
+        /* verify with Q: the batch's syndrome records first, then the P check's */
+        uint64_t nchk = 0;
+        for (size_t i = first; i < last && qres; i++)
+            nchk += tasks[i].q_state == BCP_QSTATE_CHECKED;
         for (size_t i = first; i < last; i++) {
             task *t = &tasks[i];
             nwrites += 1 + t->has2;
+            if (t->vq && t->q_state == BCP_QSTATE_CHECKED) {
+                /* dst and qd are the P and Q bodies in the input slab (only
+                 * read), the sources the chunks in holder order */
+                const int nfold = t->parity_src;
+                t->out_off = (uint64_t)ns2 * sizeof(bcp_pq_check_result);
+                pl->st2[ns2] = (bcp_stripe){(uint64_t)S->d_in + data_off(t, nfold, dir), t->out_len, nsrc2, (uint32_t)nfold, 0};
+                pl->qd[ns2] = (uint64_t)S->d_in + data_off(t, t->q_src, dir);
+                for (int k = 0; k < nfold; k++)
+                    pl->so2[nsrc2++] = (bcp_source){(uint64_t)S->d_in + data_off(t, k, dir), t->size[k]};
+                ns2++;
+                if (t->out_off + sizeof(bcp_pq_check_result) > out_used)
+                    out_used = t->out_off + sizeof(bcp_pq_check_result);
+                continue;
+            }
+            if (t->vq) {
+                t->out_off = nchk * sizeof(bcp_pq_check_result) + (uint64_t)ns * sizeof(bcp_check_result);
+                if (t->out_off + sizeof(bcp_check_result) > out_used)
+                    out_used = t->out_off + sizeof(bcp_check_result);
+            }
             if (t->pq) {
                 /* the survivors in position order, the victims' positions empty */
                 recover = 1;
@@ -1524,22 +1596,26 @@ static int pipeline_exec(bcp_pipeline *pl, const char *store_root, task *tasks, 
             }
             /* verify: dst is the parity body in the input slab (only read), the
              * sources are the chunks before it */
-            const int nfold = verify ? t->n - 1 : t->n;
+            const int nfold = verify ? t->parity_src : t->n;
             const uint64_t dst = verify ? (uint64_t)S->d_in + data_off(t, nfold, dir) : (uint64_t)S->d_out + t->out_off;
             st[ns] = (bcp_stripe){dst, t->out_len, nsrc, (uint32_t)nfold, t->max_cs > WINDOW ? WINDOW : 0};
             for (int k = 0; k < nfold; k++)
                 so[nsrc++] = (bcp_source){(uint64_t)S->d_in + data_off(t, k, dir), t->size[k]};
             ns++;
-            if (t->out_off + out_span(t) > out_used)
+            if (!t->vq && t->out_off + out_span(t) > out_used)
                 out_used = t->out_off + out_span(t);
         }
         /* device: H2D (side queue) -> kernel -> D2H (side queue) */
         if ((in_used && (rc = bcp_h2d_async(L->qh, S->d_in, S->h_in, (size_t)in_used))) ||
             (rc = bcp_event_record(S->ev_h, L->qh)) || (rc = bcp_queue_wait_event(L->qk, S->ev_h)) ||
-            (rc = verify ? bcp_check_stripes_async(L->qk, st, ns, so, nsrc, (bcp_check_result *)S->d_out)
+            (rc = verify ? bcp_check_stripes_async(L->qk, st, ns, so, nsrc,
+                                                   (bcp_check_result *)((uint8_t *)S->d_out +
+                                                                        nchk * sizeof(bcp_pq_check_result)))
                          : bcp_xor_stripes_async(L->qk, st, ns, so, nsrc)) ||
-            (ns2 && (rc = recover ? bcp_pq_recover_stripes_async(L->qk, pl->st2, ns2, pl->so2, nsrc2, pl->lost)
-                                  : bcp_pq_stripes_async(L->qk, pl->st2, ns2, pl->so2, nsrc2, pl->qd))) ||
+            (ns2 && (rc = qres      ? bcp_pq_check_stripes_async(L->qk, pl->st2, ns2, pl->so2, nsrc2, pl->qd,
+                                                                 (bcp_pq_check_result *)S->d_out)
+                          : recover ? bcp_pq_recover_stripes_async(L->qk, pl->st2, ns2, pl->so2, nsrc2, pl->lost)
+                                    : bcp_pq_stripes_async(L->qk, pl->st2, ns2, pl->so2, nsrc2, pl->qd))) ||
             (rc = bcp_event_record(S->ev_k, L->qk)) ||
             (rc = bcp_queue_wait_event(L->qd, S->ev_k)) ||
             (rc = bcp_d2h_async(L->qd, S->h_out, S->d_out, (size_t)out_used)) ||
@@ -1598,7 +1674,33 @@ static int pipeline_exec(bcp_pipeline *pl, const char *store_root, task *tasks, 
     pl->last = tm;
     if (!rc && dev_rc)
         rc = dev_rc;
-    for (size_t i = 0; i < nt && verify; i++) {
+    for (size_t i = 0; i < nt && qres; i++) {
+        const task *t = &tasks[i];
+        bcp_verify_q_item *v = &qres[t->item];
+        if (t->status == VERIFY_PENDING) { /* its batch never came back */
+            v->status = BCP_VERIFY_SKIPPED;
+            errors++;
+            continue;
+        }
+        v->status = t->status;
+        v->q_state = t->q_state;
+        if (t->status != BCP_VERIFY_MISMATCH)
+            continue;
+        v->first_bad = t->first_bad;
+        v->p_bad = t->bad_bytes;
+        v->culprit = BCP_CULPRIT_MANY; /* the P check alone names nobody */
+        if (t->q_state == BCP_QSTATE_CHECKED) {
+            const bcp_pq_check_result r = {t->first_bad, t->bad_bytes, t->q_bad, t->members};
+            int pos = -1;
+            v->q_bad = t->q_bad;
+            v->culprit = (uint32_t)bcp_pq_culprit(&r, &pos);
+            v->target = v->culprit == BCP_CULPRIT_DATA && pos < t->parity_src ? t->holders[pos]
+                        : v->culprit == BCP_CULPRIT_P                         ? t->p
+                        : v->culprit == BCP_CULPRIT_Q                         ? t->q_st
+                                                                              : -1;
+        }
+    }
+    for (size_t i = 0; i < nt && vres; i++) {
         bcp_verify_item *v = &vres[tasks[i].item];
         if (tasks[i].status == VERIFY_PENDING) { /* its batch never came back */
             v->status = BCP_VERIFY_SKIPPED;
@@ -1679,7 +1781,7 @@ int bcp_pipeline_rebuild(bcp_pipeline *pl, const char *store_root, int ntargets,
                 t->holders[t->n++] = k;
             }
     }
-    int rc = pipeline_exec(pl, store_root, tasks, nt, corrupt_fd, log, stats, t0, NULL);
+    int rc = pipeline_exec(pl, store_root, tasks, nt, corrupt_fd, log, stats, t0, NULL, NULL);
     free(tasks);
     if (stats)
         stats->refused = bcpr_count_refused(items, nitems, rebuild_target);
@@ -1745,7 +1847,7 @@ int bcp_pipeline_verify(bcp_pipeline *pl, const char *store_root, int ntargets, 
         t->holders[t->n++] = P;
     }
     bcp_run_stats rs = {0};
-    rc = pipeline_exec(pl, store_root, tasks, nt, -1, log, &rs, t0, res);
+    rc = pipeline_exec(pl, store_root, tasks, nt, -1, log, &rs, t0, res, NULL);
     bcp_verify_stats vs = {0};
     vs.items = nitems;
     vs.refused = refused;
@@ -1771,6 +1873,137 @@ int bcp_pipeline_verify(bcp_pipeline *pl, const char *store_root, int ntargets, 
 out:
     if (bad_fd >= 0)
         close(bad_fd);
+    free(tasks);
+    if (res != results)
+        free(res);
+    return rc;
+}
+
+/* One line of the culprit list, written whole. */
+static void push_culprit(int fd, const char *path, uint32_t culprit, int target)
+{
+    static const char *const kind[] = {"many", "data", "p", "q", "many"};
+    if (fd < 0)
+        return;
+    const size_t cap = strlen(path) + 32;
+    char *line = malloc(cap);
+    if (!line)
+        return;
+    const int len = snprintf(line, cap, "%s\t%s\t%d\n", path, kind[culprit <= BCP_CULPRIT_MANY ? culprit : 0], target);
+    ssize_t w = write(fd, line, (size_t)len);
+    (void)w;
+    free(line);
+}
+
+int bcp_pipeline_verify_q(bcp_pipeline *pl, const char *store_root, int ntargets, const bcp_work_item *items,
+                          size_t nitems, bcp_verify_q_item *results, const char *bad_list_path,
+                          const char *culprit_list_path, FILE *log, bcp_verify_q_stats *stats)
+{
+    if (!pl || !store_root || ntargets < 1 || ntargets > MAX_STORAGE_TARGETS || (nitems && !items))
+        return -EINVAL;
+    double t0 = now_s();
+    for (size_t i = 0; i < nitems; i++) {
+        uint64_t loc = items[i].fi.locations;
+        int P = GET_P(loc);
+        if ((uint64_t)P == NO_P)
+            continue;
+        if (!items[i].path || P >= ntargets || TEST_BIT(loc, P) || ((loc & L_MASK) >> ntargets))
+            return -EINVAL;
+    }
+    bcp_verify_q_item *res = results ? results : calloc(nitems ? nitems : 1, sizeof(*res));
+    task *tasks = calloc(nitems ? nitems : 1, sizeof(task));
+    int bad_fd = -1, culprit_fd = -1, rc = 0;
+    if (!res || !tasks) {
+        rc = -ENOMEM;
+        goto out;
+    }
+    if (bad_list_path) {
+        bad_fd = open(bad_list_path, O_WRONLY | O_CREAT | O_TRUNC | O_APPEND, S_IRUSR | S_IWUSR);
+        if (bad_fd < 0) {
+            rc = -errno;
+            goto out;
+        }
+    }
+    if (culprit_list_path) {
+        culprit_fd = open(culprit_list_path, O_WRONLY | O_CREAT | O_TRUNC | O_APPEND, S_IRUSR | S_IWUSR);
+        if (culprit_fd < 0) {
+            rc = -errno;
+            goto out;
+        }
+    }
+    uint64_t refused = 0;
+    size_t nt = 0;
+    for (size_t i = 0; i < nitems; i++) {
+        const FileInfo *fi = &items[i].fi;
+        const int P = GET_P(fi->locations);
+        res[i] = (bcp_verify_q_item){BCP_VERIFY_SKIPPED, BCP_QSTATE_NONE, BCP_CULPRIT_NONE, -1, UINT64_MAX, 0, 0};
+        if ((uint64_t)P == NO_P || (fi->locations & L_MASK) == 0)
+            continue;
+        if (!bcpi_path_ok(items[i].path, (size_t)-1)) {
+            if (log)
+                fprintf(log, "bcp_pipeline: refusing '%s': not a path inside the store\n", items[i].path);
+            refused++;
+            continue;
+        }
+        task *t = &tasks[nt++];
+        t->path = items[i].path;
+        t->p = P;
+        t->q_st = bcp_q_target(fi->locations, ntargets);
+        t->vq = 1;
+        t->q_state = BCP_QSTATE_NONE;
+        t->verify = 1;
+        t->item = i;
+        t->timestamp = fi->timestamp;
+        for (int k = 0; k < MAX_STORAGE_TARGETS; k++)
+            if (TEST_BIT(fi->locations, k))
+                t->holders[t->n++] = k;
+        t->parity_src = t->n; /* the P body, held by P; a Q body follows it (do_stat) */
+        t->holders[t->n++] = P;
+    }
+    bcp_run_stats rs = {0};
+    rc = pipeline_exec(pl, store_root, tasks, nt, -1, log, &rs, t0, NULL, res);
+    bcp_verify_q_stats vs;
+    memset(&vs, 0, sizeof(vs));
+    vs.v.items = nitems;
+    vs.v.refused = refused;
+    vs.v.bytes_read = rs.bytes_read;
+    vs.v.errors = rs.errors + (rc != 0);
+    for (size_t i = 0; i < nitems; i++) {
+        const bcp_verify_q_item *v = &res[i];
+        const int compared = v->status == BCP_VERIFY_OK || v->status == BCP_VERIFY_MISMATCH;
+        switch (v->status) {
+        case BCP_VERIFY_OK: vs.v.ok++; break;
+        case BCP_VERIFY_STALE: vs.v.stale++; break;
+        case BCP_VERIFY_NO_PARITY: vs.v.no_parity++; break;
+        case BCP_VERIFY_SIZE: vs.v.size++; break;
+        case BCP_VERIFY_MISMATCH: vs.v.mismatch++; break;
+        default: vs.v.skipped++; break;
+        }
+        if (compared) {
+            vs.q_checked += v->q_state == BCP_QSTATE_CHECKED;
+            vs.q_none += v->q_state == BCP_QSTATE_NONE;
+            vs.q_bad += v->q_state == BCP_QSTATE_BAD;
+        }
+        /* both lists after the run, in item order */
+        if (v->status == BCP_VERIFY_NO_PARITY || v->status == BCP_VERIFY_SIZE || v->status == BCP_VERIFY_MISMATCH ||
+            (compared && v->q_state == BCP_QSTATE_BAD))
+            push_corrupt(bad_fd, items[i].path);
+        if (v->status == BCP_VERIFY_MISMATCH) {
+            vs.culprit_data += v->culprit == BCP_CULPRIT_DATA;
+            vs.culprit_p += v->culprit == BCP_CULPRIT_P;
+            vs.culprit_q += v->culprit == BCP_CULPRIT_Q;
+            vs.culprit_many += v->culprit == BCP_CULPRIT_MANY;
+            push_culprit(culprit_fd, items[i].path, v->culprit, v->target);
+        }
+    }
+    vs.v.seconds = now_s() - t0;
+    if (stats)
+        *stats = vs;
+out:
+    if (bad_fd >= 0)
+        close(bad_fd);
+    if (culprit_fd >= 0)
+        close(culprit_fd);
     free(tasks);
     if (res != results)
         free(res);
@@ -1911,7 +2144,7 @@ int bcp_pipeline_rebuild2(bcp_pipeline *pl, const char *store_root, int ntargets
         nt++;
     }
     pl->r2_unrec = unrec;
-    rc = pipeline_exec(pl, store_root, tasks, nt, corrupt_fd, log, stats, t0, NULL);
+    rc = pipeline_exec(pl, store_root, tasks, nt, corrupt_fd, log, stats, t0, NULL, NULL);
     pl->r2_unrec = NULL;
     bcp_rebuild2_stats r2 = {0, 0, 0, 0};
     for (size_t i = 0; i < nitems; i++) {

@@ -8,7 +8,7 @@
 // four packed bytes of a dword at a time (mul2): no multiply, no table, no
 // LDS.  One pass over the sources yields both.
 //
-// Two forms of that pass:
+// Three forms of that pass:
 //   GEN    the epilogue stores Q, and P when the stripe has a P address;
 //   SOLVE  the sources are the survivors (lost positions have len 0 and
 //          contribute 2*q steps only), the P and Q bodies are loaded with the
@@ -16,6 +16,12 @@
 //          syndromes Ps and Qs; the epilogue stores D_x = ca*Ps ^ cb*Qs and
 //          D_y = Ps ^ D_x, each truncated to its own length.  ca, cb are
 //          per-stripe constants from the host (P lost: ca = 0, cb = g^-x).
+//   CHECK  SOLVE's prologue and pass over a complete stripe (P body
+//          required), so the accumulators are again Ps and Qs; nothing is
+//          stored.  A clean tile ends on one ballot.  Otherwise the wave
+//          locates every bad byte -- Ps only: P, Qs only: Q, both: the data
+//          position k with g^k * Ps = Qs -- and commits first offset, counts
+//          and member mask to the stripe's record (bcp_pq_check_result).
 //
 // Schedule and load shape are the descriptor fold's (bcp_kernels.hip): a
 // device-wide atomicAdd-fed tile queue, wave-contiguous lanes, 16-byte
@@ -132,8 +138,93 @@ __device__ __forceinline__ void pq_store(uint64_t d, uint64_t left, uint32_t T, 
   }
 }
 
-template <int U, bool SOLVE>
-__device__ __forceinline__ void pq_tile(const PqBatch &b, uint32_t t) {
+// ---- CHECK form: what the syndromes say ---------------------------------
+// Bit 7 of every non-zero byte of w.
+__device__ __forceinline__ uint32_t nz_bytes(uint32_t w) {
+  return (((w & 0x7f7f7f7fu) + 0x7f7f7f7fu) | w) & 0x80808080u;
+}
+
+// Bytes of the tile at or past `left` do not count (a source may be longer
+// than out_len; the bodies' tail loads are zero there already).
+template <int U>
+__device__ __forceinline__ void pq_mask_tail(v4u (&v)[U], uint32_t left, uint32_t lane_off) {
+#pragma unroll
+  for (int u = 0; u < U; u++) {
+    const uint32_t o = lane_off + (uint32_t)u * 1024u;
+#pragma unroll
+    for (int c = 0; c < 4; c++) {
+      const uint32_t at = o + (uint32_t)c * 4u;
+      const uint32_t n = left > at ? left - at : 0u;  // readable bytes of this dword
+      v[u][c] &= n >= 4u ? 0xFFFFFFFFu : ((1u << (8u * n)) - 1u);
+    }
+  }
+}
+
+// Mismatch path, every lane of the wave: Ps and Qs of this lane's vectors
+// (vector u at tile offset lane_off + u * 1024, tile at stripe offset off).
+// k is searched with mul2 alone, t = g^k * Ps against Qs on the bytes where
+// both are non-zero; g has order 255 > nsrc, so a byte matches at most one k
+// and the bytes that never matched are counted, not tracked.  One vector at a
+// time, the loop over k rolled: this path is rare and must set neither the
+// kernel's register budget nor its code size.
+template <int U>
+__device__ __forceinline__ void pq_check_commit(bcp_pq_check_result *rec, const v4u (&ps)[U], const v4u (&qs)[U],
+                                                uint32_t nsrc, uint64_t off, uint32_t lane_off) {
+  uint32_t first = 0xFFFFFFFFu, np = 0, nq = 0, nboth = 0, nfound = 0;
+  unsigned long long members = 0;
+#pragma unroll
+  for (int u = 0; u < U; u++) {
+#pragma unroll
+    for (int c = 0; c < 4; c++) {
+      const uint32_t hp = nz_bytes(ps[u][c]), hq = nz_bytes(qs[u][c]);
+      np += (uint32_t)__builtin_popcount(hp);
+      nq += (uint32_t)__builtin_popcount(hq);
+      nboth += (uint32_t)__builtin_popcount(hp & hq);
+      if (hp & ~hq) members |= BCP_PQ_BAD_P;
+      if (hq & ~hp) members |= BCP_PQ_BAD_Q;
+      if (hp | hq) {
+        const uint32_t o = lane_off + (uint32_t)u * 1024u + (uint32_t)c * 4u + ((uint32_t)__builtin_ctz(hp | hq) >> 3);
+        first = o < first ? o : first;
+      }
+    }
+  }
+#pragma unroll
+  for (int u = 0; u < U; u++) {
+    v4u t = ps[u], both;
+#pragma unroll
+    for (int c = 0; c < 4; c++) both[c] = nz_bytes(ps[u][c]) & nz_bytes(qs[u][c]);
+#pragma unroll 1
+    for (uint32_t k = 0; k < nsrc; k++) {
+      uint32_t hit = 0;
+#pragma unroll
+      for (int c = 0; c < 4; c++) hit += (uint32_t)__builtin_popcount(both[c] & ~nz_bytes(t[c] ^ qs[u][c]));
+      if (hit) members |= 1ull << k;
+      nfound += hit;
+      t = mul2(t);
+    }
+  }
+  if (nfound < nboth) members |= BCP_PQ_BAD_NOWHERE;
+  unsigned long long f = first == 0xFFFFFFFFu ? ~0ull : off + first, cp = np, cq = nq;
+  for (int o = 32; o > 0; o >>= 1) {
+    const unsigned long long fo = __shfl_xor(f, o, 64);
+    f = fo < f ? fo : f;
+    cp += __shfl_xor(cp, o, 64);
+    cq += __shfl_xor(cq, o, 64);
+    members |= __shfl_xor(members, o, 64);
+  }
+  if ((threadIdx.x & 63u) == 0 && members) {
+    __hip_atomic_fetch_min((unsigned long long *)&rec->first_bad, f, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    __hip_atomic_fetch_add((unsigned long long *)&rec->p_bad, cp, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    __hip_atomic_fetch_add((unsigned long long *)&rec->q_bad, cq, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    __hip_atomic_fetch_or((unsigned long long *)&rec->members, members, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  }
+}
+
+enum PqForm { kPqGen = 0, kPqSolve = 1, kPqCheck = 2 };
+
+template <int U, PqForm F>
+__device__ __forceinline__ void pq_tile(const PqBatch &b, uint32_t t, bcp_pq_check_result *res) {
+  constexpr bool SOLVE = F == kPqSolve;
   constexpr uint32_t T = (uint32_t)kBlock * U * 16u;
   const_as<PqTile> *tr = cst(b.tiles) + t;
   const_as<PqStripe> *d = cst(b.stripes) + tr->stripe;
@@ -145,7 +236,7 @@ __device__ __forceinline__ void pq_tile(const PqBatch &b, uint32_t t) {
   v4u p[U], q[U], qb[U];
 #pragma unroll
   for (int u = 0; u < U; u++) p[u] = q[u] = qb[u] = zero4();
-  if constexpr (SOLVE) {
+  if constexpr (F != kPqGen) {
     // the P and Q bodies: p starts as P, the Q body joins after the Horner pass
     const uint64_t pp = d->p;
     if (out_left >= T) {
@@ -181,7 +272,19 @@ __device__ __forceinline__ void pq_tile(const PqBatch &b, uint32_t t) {
     case 1: pq_group<1, U>(p, q, run, off, T, lane_off); break;
     default: break;
   }
-  if constexpr (SOLVE) {
+  if constexpr (F == kPqCheck) {
+#pragma unroll
+    for (int u = 0; u < U; u++) q[u] ^= qb[u];  // p = Ps, q = Qs
+    if (out_left < T) {  // the stripe's last tile (uniform)
+      pq_mask_tail<U>(p, (uint32_t)out_left, lane_off);
+      pq_mask_tail<U>(q, (uint32_t)out_left, lane_off);
+    }
+    v4u any = p[0] | q[0];
+#pragma unroll
+    for (int u = 1; u < U; u++) any |= p[u] | q[u];
+    if (__ballot((any[0] | any[1] | any[2] | any[3]) != 0u) == 0) return;  // clean: no store, no atomic
+    pq_check_commit<U>(res + tr->stripe, p, q, d->nsrc, off, lane_off);
+  } else if constexpr (SOLVE) {
 #pragma unroll
     for (int u = 0; u < U; u++) q[u] ^= qb[u];  // p = Ps, q = Qs
     v4u dx[U];
@@ -203,8 +306,8 @@ __device__ __forceinline__ void pq_tile(const PqBatch &b, uint32_t t) {
   }
 }
 
-template <int U, bool SOLVE>
-__global__ __launch_bounds__(kBlock) void pq_desc(PqBatch b) {
+template <int U, PqForm F>
+__device__ __forceinline__ void pq_body(const PqBatch &b, bcp_pq_check_result *res) {
   // Work queue, one tile per grab (two LDS slots as in stream_body).
   __shared__ uint32_t next[2];
   if (threadIdx.x == 0) next[0] = queue_grab(b.ctr, b.base);
@@ -212,12 +315,29 @@ __global__ __launch_bounds__(kBlock) void pq_desc(PqBatch b) {
   uint32_t t = __builtin_amdgcn_readfirstlane(next[0]);
   int slot = 0;
   while (t < b.ntiles) {
-    pq_tile<U, SOLVE>(b, t);
+    pq_tile<U, F>(b, t, res);
     slot ^= 1;
     if (threadIdx.x == 0) next[slot] = queue_grab(b.ctr, b.base);
     __syncthreads();
     t = __builtin_amdgcn_readfirstlane(next[slot]);
   }
+}
+
+template <int U, bool SOLVE>
+__global__ __launch_bounds__(kBlock) void pq_desc(PqBatch b) {
+  pq_body<U, SOLVE ? kPqSolve : kPqGen>(b, nullptr);
+}
+
+// The CHECK form (bcp_pq_check_stripes_async): same tiles, same queue, one
+// record per stripe in res (initialised by pq_check_init before the launch).
+template <int U>
+__global__ __launch_bounds__(kBlock) void pq_check_desc(PqBatch b, bcp_pq_check_result *res) {
+  pq_body<U, kPqCheck>(b, res);
+}
+
+__global__ __launch_bounds__(kBlock) void pq_check_init(bcp_pq_check_result *res, uint32_t n) {
+  const uint32_t i = blockIdx.x * kBlock + threadIdx.x;
+  if (i < n) res[i] = bcp_pq_check_result{~0ull, 0ull, 0ull, 0ull};
 }
 
 hipError_t launch_pq(hipStream_t st, int grid, int vecs, bool solve, const PqBatch &b) {
@@ -229,6 +349,19 @@ hipError_t launch_pq(hipStream_t st, int grid, int vecs, bool solve, const PqBat
     if (solve) hipLaunchKernelGGL((pq_desc<4, true>), dim3(grid), dim3(kBlock), 0, st, b);
     else hipLaunchKernelGGL((pq_desc<4, false>), dim3(grid), dim3(kBlock), 0, st, b);
   }
+  return hipGetLastError();
+}
+
+hipError_t launch_pq_check_init(hipStream_t st, bcp_pq_check_result *res, uint32_t n) {
+  if (!n) return hipSuccess;
+  hipLaunchKernelGGL(pq_check_init, dim3((n + kBlock - 1) / kBlock), dim3(kBlock), 0, st, res, n);
+  return hipGetLastError();
+}
+
+hipError_t launch_pq_check(hipStream_t st, int grid, int vecs, const PqBatch &b, bcp_pq_check_result *res) {
+  if (grid <= 0 || !pq_vecs_ok(vecs) || !res) return hipErrorInvalidValue;
+  if (vecs == 8) hipLaunchKernelGGL((pq_check_desc<8>), dim3(grid), dim3(kBlock), 0, st, b, res);
+  else hipLaunchKernelGGL((pq_check_desc<4>), dim3(grid), dim3(kBlock), 0, st, b, res);
   return hipGetLastError();
 }
 

@@ -1,4 +1,6 @@
 /* bcp_pq_host.c -- host-only pieces of Q parity (no device needed). */
+#include <errno.h>
+
 #include "bcp.h"
 #include "bcp_task.h"
 
@@ -13,4 +15,18 @@ int bcp_q_target(uint64_t locations, int ntargets) {
         if (!TEST_BIT(locations, t)) return t;
     }
     return -1;
+}
+
+/* The single member a syndrome record blames, if it blames one. */
+int bcp_pq_culprit(const bcp_pq_check_result *r, int *position) {
+    if (!r) return -EINVAL;
+    if (position) *position = -1;
+    const uint64_t m = r->members;
+    if (!m) return BCP_CULPRIT_NONE;
+    if ((m & (m - 1)) || (m & BCP_PQ_BAD_NOWHERE)) return BCP_CULPRIT_MANY;
+    if (m == BCP_PQ_BAD_P) return BCP_CULPRIT_P;
+    if (m == BCP_PQ_BAD_Q) return BCP_CULPRIT_Q;
+    if (m >> BCP_MAX_SOURCES) return BCP_CULPRIT_MANY; /* bits above 58 are no member */
+    if (position) *position = __builtin_ctzll(m);
+    return BCP_CULPRIT_DATA;
 }

@@ -37,7 +37,8 @@
  *       target is lost too; chunks are rebuilt from P, from Q or from both
  *       (bcp_pipeline_rebuild2), the paths that cannot be go to --lost FILE and
  *       the exit status is then 1.
- *   bcp parity-verify [--db DIR] [--bad FILE] [--read PATH] <store_root> <ntargets>
+ *   bcp parity-verify [--db DIR] [--bad FILE] [--read PATH] [--q [--culprits FILE]]
+ *                     <store_root> <ntargets>
  *       The scrub (no counterpart in the reference): for every item of the
  *       database (default <root>/st0/db) the batched pipeline reads the chunks
  *       and the parity body and compares them on the device
@@ -46,6 +47,13 @@
  *       has the wrong size or differs.  Exit 0 when nothing is NO_PARITY, SIZE
  *       or MISMATCH, nothing was refused and no read or device error occurred
  *       (stale items -- chunks modified since the last round -- are clean).
+ *       --q: the scrub with Q (bcp_pipeline_verify_q): an item's Q file is
+ *       read and checked in the same pass, and a mismatch names the one file
+ *       that is wrong -- a chunk, P or Q -- where the syndromes allow.  A
+ *       second summary line has the Q states and the culprits; --culprits FILE
+ *       gets one line "path<TAB>data|p|q|many<TAB>target" per mismatch; --bad
+ *       also lists the items whose Q file is missing or out of order, and
+ *       those make the exit status 1 too.
  *
  * Items whose path would leave the store (absolute, "..") are skipped and
  * counted as refused; a run with refused items exits 1.
@@ -72,7 +80,8 @@ static int usage(void)
           "       bcp parity-rebuild [--pipeline|--protocol|--procs] [--fold MODE] [--read PATH] [--lanes N]\n"
           "                          [--db DIR] [--corrupt FILE] [--also TARGET] [--lost FILE]\n"
           "                          <store_root> <ntargets> <target>\n"
-          "       bcp parity-verify [--db DIR] [--bad FILE] [--read PATH] <store_root> <ntargets>\n"
+          "       bcp parity-verify [--db DIR] [--bad FILE] [--read PATH] [--q [--culprits FILE]]\n"
+          "                         <store_root> <ntargets>\n"
           "       engine: --pipeline (default: batched pipeline on every GPU) | --protocol (per-rank\n"
           "               process_task, ranks as threads) | --procs (ranks as processes)\n"
           "       MODE (protocol P-role fold): pipelined (default) | batched\n"
@@ -80,7 +89,9 @@ static int usage(void)
           "            direct (O_DIRECT)\n"
           "       --read applies to the pipeline only, --fold to --protocol / --procs only\n"
           "       --q (also write Q parity files) and --also TARGET (a second lost target; --lost FILE lists\n"
-          "            what cannot be rebuilt) apply to the pipeline only\n",
+          "            what cannot be rebuilt) apply to the pipeline only\n"
+          "       parity-verify --q also reads and checks the Q files and names the wrong file of a mismatch;\n"
+          "            --culprits FILE (with --q only) lists path, data|p|q|many and the storage target\n",
           stderr);
     return 1;
 }
@@ -434,20 +445,24 @@ static int cmd_rebuild(int argc, char **argv)
 
 static int cmd_verify(int argc, char **argv)
 {
-    const char *db = NULL, *bad = NULL;
-    int i = 0;
+    const char *db = NULL, *bad = NULL, *culprits = NULL;
+    int i = 0, with_q = 0;
     for (; i < argc && argv[i][0] == '-'; i++) {
         if (!strcmp(argv[i], "--db") && i + 1 < argc)
             db = argv[++i];
         else if (!strcmp(argv[i], "--bad") && i + 1 < argc)
             bad = argv[++i];
+        else if (!strcmp(argv[i], "--culprits") && i + 1 < argc)
+            culprits = argv[++i];
+        else if (!strcmp(argv[i], "--q"))
+            with_q = 1;
         else if (!strcmp(argv[i], "--read") && i + 1 < argc) {
             if ((g_read_mode = read_mode_arg(argv[++i])) < 0)
                 return usage();
         } else
             return usage();
     }
-    if (argc - i != 2)
+    if (argc - i != 2 || (culprits && !with_q))
         return usage();
     const char *root = argv[i];
     const int ntargets = atoi(argv[i + 1]);
@@ -463,7 +478,9 @@ static int cmd_verify(int argc, char **argv)
     bcp_work_item *items = NULL;
     size_t n = 0;
     bcp_verify_stats vs;
+    bcp_verify_q_stats qs;
     memset(&vs, 0, sizeof(vs));
+    memset(&qs, 0, sizeof(qs));
     int rc = stat(db, &sb) == 0 ? 0 : -errno;
     if (!rc)
         rc = bcp_pdb_open(db, DB_VERSION, &pdb);
@@ -474,7 +491,10 @@ static int cmd_verify(int argc, char **argv)
     if (!rc) {
         bcp_pipeline *pl = NULL;
         rc = pipeline_on_all_gpus(&pl, 0);
-        if (!rc)
+        if (!rc && with_q) {
+            rc = bcp_pipeline_verify_q(pl, root, ntargets, items, n, NULL, bad, culprits, stderr, &qs);
+            vs = qs.v;
+        } else if (!rc)
             rc = bcp_pipeline_verify(pl, root, ntargets, items, n, NULL, bad, stderr, &vs);
         if (pl)
             bcp_pipeline_destroy(pl);
@@ -488,7 +508,12 @@ static int cmd_verify(int argc, char **argv)
            (unsigned long long)vs.no_parity, (unsigned long long)vs.size, (unsigned long long)vs.mismatch,
            (unsigned long long)vs.skipped, (unsigned long long)vs.refused, vs.errors, vs.seconds,
            vs.bytes_read / 1048576.0);
-    return (vs.no_parity || vs.size || vs.mismatch || vs.refused || vs.errors) ? 1 : 0;
+    if (with_q)
+        printf("q files: %llu checked, %llu none, %llu bad; culprits: %llu data, %llu p, %llu q, %llu many\n",
+               (unsigned long long)qs.q_checked, (unsigned long long)qs.q_none, (unsigned long long)qs.q_bad,
+               (unsigned long long)qs.culprit_data, (unsigned long long)qs.culprit_p,
+               (unsigned long long)qs.culprit_q, (unsigned long long)qs.culprit_many);
+    return (vs.no_parity || qs.q_bad || vs.size || vs.mismatch || vs.refused || vs.errors) ? 1 : 0;
 }
 
 int main(int argc, char **argv)

@@ -49,7 +49,9 @@ extern "C" {
  * bcp_check_stripes_async / bcp_check_result, and the "last_desc_form"
  * value 3; Q parity's bcp_pq_stripes_async / bcp_pq_recover_stripes_async /
  * bcp_pq_lost / bcp_q_target, the "last_desc_form" values 4 and 5 and the
- * option "pq_blocks_per_cu".
+ * option "pq_blocks_per_cu"; the Q-aware scrub's
+ * bcp_pq_check_stripes_async / bcp_pq_check_result / bcp_pq_culprit and the
+ * "last_desc_form" value 6.
  * 3 (r05): the pipeline's MAP read mode (BCP_READ_MAP), its
  * bcp_pipeline_timing fields and bcp_host_register_dma_src removed.
  * 2 (r04): bcp_task.h's bcp_run_stats gained `refused`, bcp_pipeline_opts
@@ -215,6 +217,42 @@ typedef struct bcp_pq_lost {
  * position whose source has len != 0 and for len_x or len_y above out_len. */
 int bcp_pq_recover_stripes_async(bcp_queue *q, const bcp_stripe *stripes, uint32_t nstripes,
                                  const bcp_source *sources, uint32_t nsources, const bcp_pq_lost *lost);
+
+/* One record per stripe of a syndrome check (bcp_pq_check_stripes_async).
+ * With Ps = P ^ XOR_k D_k and Qs = Q ^ XOR_k g^k * D_k, a byte j is bad when
+ * Ps[j] or Qs[j] is non-zero, and names its member: Ps only, P; Qs only, Q;
+ * both, the data position k < nsrc with g^k * Ps[j] = Qs[j] (unique: g has
+ * order 255), or nowhere when there is no such k. */
+#define BCP_PQ_BAD_P        (1ull << 56)
+#define BCP_PQ_BAD_Q        (1ull << 57)
+#define BCP_PQ_BAD_NOWHERE  (1ull << 58)
+typedef struct bcp_pq_check_result {
+    uint64_t first_bad;  /* smallest j in [0,out_len) with Ps[j] or Qs[j] != 0; UINT64_MAX if none */
+    uint64_t p_bad;      /* bytes with Ps != 0 */
+    uint64_t q_bad;      /* bytes with Qs != 0 */
+    uint64_t members;    /* OR over the bad bytes: bit k<56 data position k, BAD_P, BAD_Q, BAD_NOWHERE */
+} bcp_pq_check_result;
+/* Syndromes of every stripe against its P and Q bodies, nothing stored but the
+ * records.  stripes[s].dst = P body, q_body[s] = Q body: both required when
+ * out_len > 0, out_len readable bytes, only read.  Sources in position order,
+ * lost or missing members with len 0; window must be 0.  results_dev:
+ * nstripes records in device memory, fully written by this call's work for
+ * every stripe -- {UINT64_MAX, 0, 0, 0} for a clean one, also for out_len == 0
+ * and for batches with no tile at all.  All four fields are exact.  Nothing is
+ * read outside [body, body+out_len) or outside a source's len. */
+int bcp_pq_check_stripes_async(bcp_queue *q, const bcp_stripe *stripes, uint32_t nstripes,
+                               const bcp_source *sources, uint32_t nsources,
+                               const uint64_t *q_body, bcp_pq_check_result *results_dev);
+/* Which single member a record blames (pure host arithmetic, no device,
+ * bcp_pq_host.c).  Returns the kind, or -EINVAL for a null record;
+ * *position (may be null) is the data position for DATA, else -1. */
+#define BCP_CULPRIT_NONE 0   /* members == 0 */
+#define BCP_CULPRIT_DATA 1   /* exactly one bit k < 56: *position = k */
+#define BCP_CULPRIT_P    2
+#define BCP_CULPRIT_Q    3
+#define BCP_CULPRIT_MANY 4   /* more than one bit, or BAD_NOWHERE: not a single-member fault */
+int bcp_pq_culprit(const bcp_pq_check_result *r, int *position);
+
 /* Storage target of an item's Q file (pure host arithmetic, no device):
  * `locations` as in bcp_task.h's FileInfo (bits 0..55 chunk holders, bits
  * 56..63 the parity target P).  The first of P+1, P+2, ... (mod ntargets)
@@ -333,7 +371,8 @@ int bcp_set_option(bcp_engine *eng, const char *key, int value);
  * "last_desc_vecs" and "last_desc_form" (descriptor kernel: 1 = desc_tiles +
  * xor_desc, 2 = xor_desc_args, 3 = desc_tiles + the check kernel of
  * bcp_check_stripes_async, 4 = the P + Q kernel of bcp_pq_stripes_async,
- * 5 = its recovery form, bcp_pq_recover_stripes_async). */
+ * 5 = its recovery form, bcp_pq_recover_stripes_async, 6 = its syndrome
+ * form, bcp_pq_check_stripes_async). */
 int bcp_get_option(bcp_engine *eng, const char *key, int *value);
 /* Timer slots for bcp_queue_mark / bcp_queue_elapsed_ms. */
 #define BCP_TIMER_SLOTS 64

@@ -684,6 +684,41 @@ typedef struct {
 int bcp_pipeline_verify(bcp_pipeline *pl, const char *store_root, int ntargets, const bcp_work_item *items,
                         size_t nitems, bcp_verify_item *results, const char *bad_list_path, FILE *log,
                         bcp_verify_stats *stats);
+/* Scrub with Q (added under ABI 4): bcp_pipeline_verify's verdicts, and for
+ * an item with a Q file the syndromes of P and Q in one pass
+ * (bcp_pq_check_stripes_async), which name the one file that is wrong.
+ * bcp_pipeline_verify itself is unchanged, with Q on or off.  Per item:
+ * SKIPPED, STALE, NO_PARITY and SIZE as above, decided from the P file; then
+ * the Q state, from bcp_q_target, the header's maximum and a stat of
+ * parityq/<path> (a Q file at a former Q target is never looked at): */
+#define BCP_QSTATE_CHECKED 0  /* Q body read and compared with P in one pass */
+#define BCP_QSTATE_NONE    1  /* no Q by rule: no Q target, or max(header) > BCP_WINDOW_BYTES */
+#define BCP_QSTATE_BAD     2  /* should have Q: file missing, size != 8n + max(header), or its header != P's */
+/* A CHECKED item's chunks, P body and Q body (file offset 8n) are read;
+ * NONE and BAD items go through bcp_check_stripes_async exactly as in
+ * bcp_pipeline_verify (p_bad = bad_bytes, q_bad = 0).  A batch may make two
+ * launches; only the records come back, 32 or 16 bytes per item. */
+typedef struct {
+    uint32_t status;     /* BCP_VERIFY_*, same values and precedence as bcp_pipeline_verify */
+    uint32_t q_state;    /* meaningful when status is OK or MISMATCH */
+    uint32_t culprit;    /* MISMATCH: BCP_CULPRIT_* (bcp.h); for q_state != CHECKED always BCP_CULPRIT_MANY */
+    int32_t  target;     /* storage target of the culprit (DATA: that holder; P; Q), else -1 */
+    uint64_t first_bad, p_bad, q_bad;
+} bcp_verify_q_item;
+typedef struct { bcp_verify_stats v; uint64_t q_checked, q_none, q_bad,
+                 culprit_data, culprit_p, culprit_q, culprit_many; } bcp_verify_q_stats;
+/* results, bad_list_path, validation and refused paths as bcp_pipeline_verify;
+ * the bad list also receives the items with q_state == BAD (status OK or
+ * MISMATCH).  culprit_list_path (or NULL; created and truncated) receives one
+ * line per MISMATCH item, in item order: path<TAB>data|p|q|many<TAB>target.
+ * A data position maps to its holder as in the Q format: the j-th holder in
+ * ascending target order has position j.  The q_* and culprit_* counts are
+ * over the OK and MISMATCH items and over the MISMATCH items.  bytes_read
+ * counts the Q bodies too.  Nothing under the store is created, modified or
+ * unlinked. */
+int bcp_pipeline_verify_q(bcp_pipeline *pl, const char *store_root, int ntargets, const bcp_work_item *items,
+                          size_t nitems, bcp_verify_q_item *results, const char *bad_list_path,
+                          const char *culprit_list_path, FILE *log, bcp_verify_q_stats *stats);
 /* ---- Q parity (a second, Reed-Solomon parity per item; added under ABI 4) --
  * With Q on, bcp_pipeline_run and bcp_gen_round_pipeline also write, per item,
  *   <root>/st<q>/parityq/<path>,  q = bcp_q_target(locations, ntargets):
