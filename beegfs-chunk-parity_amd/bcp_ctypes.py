@@ -189,6 +189,12 @@ _SIGS = {
                                       ctypes.c_uint32, ctypes.POINTER(PqLost)], ctypes.c_int),
     "bcp_pq_check_stripes_async": ([_V, ctypes.POINTER(Stripe), ctypes.c_uint32, ctypes.POINTER(Source),
                                     ctypes.c_uint32, ctypes.POINTER(ctypes.c_uint64), _V], ctypes.c_int),
+    "bcp_pq_stripes_win_async": ([_V, ctypes.POINTER(Stripe), ctypes.c_uint32, ctypes.POINTER(Source),
+                                  ctypes.c_uint32, ctypes.POINTER(ctypes.c_uint64)], ctypes.c_int),
+    "bcp_pq_recover_stripes_win_async": ([_V, ctypes.POINTER(Stripe), ctypes.c_uint32, ctypes.POINTER(Source),
+                                          ctypes.c_uint32, ctypes.POINTER(PqLost)], ctypes.c_int),
+    "bcp_pq_check_stripes_win_async": ([_V, ctypes.POINTER(Stripe), ctypes.c_uint32, ctypes.POINTER(Source),
+                                        ctypes.c_uint32, ctypes.POINTER(ctypes.c_uint64), _V], ctypes.c_int),
     "bcp_pq_culprit": ([ctypes.POINTER(PqCheckResult), ctypes.POINTER(ctypes.c_int)], ctypes.c_int),
     "bcp_q_target": ([ctypes.c_uint64, ctypes.c_int], ctypes.c_int),
     "bcp_xor_parity": ([_V, ctypes.c_size_t, _V, ctypes.c_int], ctypes.c_int),
@@ -261,6 +267,7 @@ _SIGS = {
                                ctypes.POINTER(VerifyQItem), ctypes.c_char_p, ctypes.c_char_p, _V,
                                ctypes.POINTER(VerifyQStats)], ctypes.c_int),
     "bcp_pipeline_set_q_parity": ([_V, ctypes.c_int], ctypes.c_int),
+    "bcp_pipeline_set_q_windowed": ([_V, ctypes.c_int], ctypes.c_int),
     "bcp_pipeline_q_stats": ([_V, ctypes.POINTER(ctypes.c_uint64), ctypes.POINTER(ctypes.c_uint64),
                               ctypes.POINTER(ctypes.c_uint64)], ctypes.c_int),
     "bcp_pipeline_rebuild2": ([_V, ctypes.c_char_p, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.POINTER(WorkItem),
@@ -505,29 +512,33 @@ class Queue:
         so = (Source * max(len(sources), 1))(*[Source(*s) for s in sources])
         call("bcp_check_stripes_async", self.h, st, len(stripes), so, len(sources), _V(results_ptr))
 
-    def pq_stripes(self, stripes, sources, q_dst):
+    def pq_stripes(self, stripes, sources, q_dst, windowed=False):
         """P and Q of every stripe: stripes as in xor_stripes (dst = P body, 0: no P), q_dst: the
-        Q body of each stripe; source k of a stripe's run has coefficient g^k."""
+        Q body of each stripe; source k of a stripe's run has coefficient g^k.  windowed: the _win
+        entry point, where a stripe's window may be a multiple of 32768 (P and Q over the replayed
+        streams); pq_recover and pq_check likewise."""
         st = (Stripe * max(len(stripes), 1))(*[Stripe(*s) for s in stripes])
         so = (Source * max(len(sources), 1))(*[Source(*s) for s in sources])
         qd = (ctypes.c_uint64 * max(len(q_dst), 1))(*q_dst)
-        call("bcp_pq_stripes_async", self.h, st, len(stripes), so, len(sources), qd)
+        call("bcp_pq_stripes_win_async" if windowed else "bcp_pq_stripes_async", self.h, st, len(stripes), so, len(sources), qd)
 
-    def pq_recover(self, stripes, sources, lost):
+    def pq_recover(self, stripes, sources, lost, windowed=False):
         """lost: one PqLost (or tuple of its fields: p, q, x, y, dst_x, len_x, dst_y, len_y) per
         stripe; the stripes list the survivors in position order, lost positions with len 0."""
         st = (Stripe * max(len(stripes), 1))(*[Stripe(*s) for s in stripes])
         so = (Source * max(len(sources), 1))(*[Source(*s) for s in sources])
         lo = (PqLost * max(len(lost), 1))(*[x if isinstance(x, PqLost) else PqLost(*x) for x in lost])
-        call("bcp_pq_recover_stripes_async", self.h, st, len(stripes), so, len(sources), lo)
+        call("bcp_pq_recover_stripes_win_async" if windowed else "bcp_pq_recover_stripes_async", self.h, st,
+             len(stripes), so, len(sources), lo)
 
-    def pq_check(self, stripes, sources, q_body, results_ptr: int):
+    def pq_check(self, stripes, sources, q_body, results_ptr: int, windowed=False):
         """Syndromes of every stripe: stripes as in pq_stripes but dst = P body and q_body[s] = Q body
         are only read; results_ptr: device memory for len(stripes) PqCheckResult records."""
         st = (Stripe * max(len(stripes), 1))(*[Stripe(*s) for s in stripes])
         so = (Source * max(len(sources), 1))(*[Source(*s) for s in sources])
         qb = (ctypes.c_uint64 * max(len(q_body), 1))(*q_body)
-        call("bcp_pq_check_stripes_async", self.h, st, len(stripes), so, len(sources), qb, _V(results_ptr))
+        call("bcp_pq_check_stripes_win_async" if windowed else "bcp_pq_check_stripes_async", self.h, st,
+             len(stripes), so, len(sources), qb, _V(results_ptr))
 
     def fill_synthetic(self, dptr: int, nbytes: int, seed: int, byte_offset: int = 0):
         call("bcp_dev_fill_synthetic_async", self.h, _V(dptr), nbytes, seed, byte_offset)
@@ -904,6 +915,11 @@ class Pipeline:
     def set_q_parity(self, on: bool):
         """Runs also write Q files (<root>/st<q>/parityq/<path>) when on; off by default."""
         call("bcp_pipeline_set_q_parity", self.h, int(bool(on)))
+
+    def set_q_windowed(self, on: bool):
+        """Items past the 10 MiB window have Q files too (run with Q on, rebuild2, verify_q); off by
+        default.  `on` goes through as it is: anything but 0 or 1 is -EINVAL."""
+        call("bcp_pipeline_set_q_windowed", self.h, int(on))
 
     def q_stats(self) -> dict:
         """Q files of the last run: written, and items left with P only (no Q target / windowed)."""

@@ -42,7 +42,7 @@ struct bcp_engine {
   pthread_mutex_t lock = PTHREAD_MUTEX_INITIALIZER;
   std::atomic<int> last_stream_vecs{0};  // U of the latest xor_stream launch (tools)
   std::atomic<int> last_desc_vecs{0};    // U of the latest descriptor-kernel launch (tools)
-  std::atomic<int> last_desc_form{0};    // 1 xor_desc (desc_tiles), 2 xor_desc_args, 3 check_desc, 4 / 5 / 6 pq_desc gen / solve / check
+  std::atomic<int> last_desc_form{0};    // 1 xor_desc (desc_tiles), 2 xor_desc_args, 3 check_desc, 4 / 5 / 6 pq_desc gen / solve / check, 7 / 8 / 9 their windowed forms
 };
 
 namespace {
@@ -1228,14 +1228,21 @@ const Gf256 g_gf;
 // The staged tables are the stripes' records, their source runs copied in the
 // caller's order, and one record per tile; they go through stage_tables with
 // the pointer-table threshold, since the kernel reads them once per tile.
+// `win` (the _win entry points) admits stripes with a window; a batch that has
+// one goes to the windowed kernels with two more tables behind the tiles
+// (PqWin per staged source, off mod W per tile), a batch that has none is the
+// plain launch.
 static int submit_pq(bcp_queue *q, const bcp_stripe *stripes, uint32_t nstripes, const bcp_source *sources,
                      uint32_t nsources, const uint64_t *q_dst, const bcp_pq_lost *lost,
-                     bcp_pq_check_result *check = nullptr) {
+                     bcp_pq_check_result *check = nullptr, bool win = false) {
   bcp_engine *e = q->eng;
   uint64_t tiles8 = 0, nstaged = 0;
+  bool windowed = false;
   for (uint32_t i = 0; i < nstripes; i++) {
     const bcp_stripe &s = stripes[i];
-    if (s.window != 0 || s.nsrc > BCP_MAX_SOURCES) return -EINVAL;
+    if (s.window != 0 && (!win || s.window % kPqWindowUnit != 0)) return -EINVAL;
+    if (s.nsrc > BCP_MAX_SOURCES) return -EINVAL;
+    windowed = windowed || s.window != 0;
     if ((uint64_t)s.first_src + s.nsrc > nsources) return -EINVAL;
     for (uint32_t k = 0; k < s.nsrc; k++) {
       const bcp_source &x = sources[s.first_src + k];
@@ -1281,7 +1288,11 @@ static int submit_pq(bcp_queue *q, const bcp_stripe *stripes, uint32_t nstripes,
   const uint32_t ntiles = (uint32_t)ntiles64;
   const size_t off_src = (size_t)nstripes * sizeof(PqStripe);
   const size_t off_tiles = (off_src + (size_t)nstaged * sizeof(bcp_source) + 15) & ~(size_t)15;
-  const size_t bytes = off_tiles + (size_t)ntiles * sizeof(PqTile);
+  // windowed batch: PqWin[nstaged] and offw[ntiles] behind the tiles
+  const size_t off_win = (off_tiles + (size_t)ntiles * sizeof(PqTile) + 15) & ~(size_t)15;
+  const size_t off_offw = off_win + (size_t)nstaged * sizeof(PqWin);
+  const size_t bytes =
+      windowed ? off_offw + (size_t)ntiles * sizeof(uint64_t) : off_tiles + (size_t)ntiles * sizeof(PqTile);
   DescSlot *slot = nullptr;
   int rc = ring_acquire(q, bytes, &slot);
   if (rc) return rc;
@@ -1290,6 +1301,8 @@ static int submit_pq(bcp_queue *q, const bcp_stripe *stripes, uint32_t nstripes,
   PqStripe *hs = (PqStripe *)h;
   bcp_source *hso = (bcp_source *)(h + off_src);
   PqTile *ht = (PqTile *)(h + off_tiles);
+  PqWin *hw = windowed ? (PqWin *)(h + off_win) : nullptr;
+  uint64_t *hoffw = windowed ? (uint64_t *)(h + off_offw) : nullptr;
   // prefix sums first, so that the records can be written by several threads
   std::vector<uint32_t> tile0(nstripes);
   {
@@ -1334,6 +1347,16 @@ static int submit_pq(bcp_queue *q, const bcp_stripe *stripes, uint32_t nstripes,
       if (s.nsrc) memcpy(hso + r.first_src, sources + s.first_src, (size_t)s.nsrc * sizeof(bcp_source));
       const uint32_t n = (uint32_t)tiles_of(i);
       for (uint32_t j = 0; j < n; j++) ht[tile0[i] + j] = PqTile{i, j};
+      if (windowed) {
+        const uint64_t W = s.window;
+        for (uint32_t k = 0; k < s.nsrc; k++) {
+          const uint64_t len = sources[s.first_src + k].len;
+          const uint64_t lw = W && len ? (len - 1) / W : 0;
+          // (lw + 1) * W cannot wrap for a len the device can address; a stripe without a window never replays
+          hw[r.first_src + k] = W && len ? PqWin{lw * W, (lw + 1) * W} : PqWin{0, ~0ull};
+        }
+        for (uint32_t j = 0; j < n; j++) hoffw[tile0[i] + j] = W ? ((uint64_t)j * T) % W : 0;
+      }
     }
   });
   char *d = nullptr;
@@ -1345,16 +1368,22 @@ static int submit_pq(bcp_queue *q, const bcp_stripe *stripes, uint32_t nstripes,
   b.ntiles = ntiles;
   b.ctr = q->qctr;
   b.base = q->qbase;
+  PqBatchWin bw;
+  bw.b = b;
+  bw.w.win = (const PqWin *)(d + off_win);
+  bw.w.offw = (const uint64_t *)(d + off_offw);
   int grid = e->tuning.desc_grid > 0 ? e->tuning.desc_grid : e->num_cus * e->tuning.pq_blocks_per_cu;
   if (grid <= 0) grid = 256;
   if ((uint32_t)grid > ntiles) grid = (int)ntiles;
   if (q->broken) return -EIO;
   (void)hipGetLastError();  // see launch_stream
-  const hipError_t le =
-      check ? launch_pq_check(q->stream, grid, vecs, b, check) : launch_pq(q->stream, grid, vecs, lost != nullptr, b);
+  const int form = check ? 2 : lost ? 1 : 0;
+  const hipError_t le = windowed ? launch_pq_win(q->stream, grid, vecs, form, bw, check)
+                        : check  ? launch_pq_check(q->stream, grid, vecs, b, check)
+                                 : launch_pq(q->stream, grid, vecs, lost != nullptr, b);
   if (le == hipSuccess) {
     e->last_desc_vecs.store(vecs, std::memory_order_relaxed);
-    e->last_desc_form.store(check ? 6 : lost ? 5 : 4, std::memory_order_relaxed);
+    e->last_desc_form.store((windowed ? 7 : 4) + form, std::memory_order_relaxed);
   }
   if ((rc = queue_launched(q, le, (uint64_t)ntiles + (uint64_t)grid))) return rc;
   HIP_RC(hipEventRecord(slot->done, q->stream));
@@ -1388,6 +1417,37 @@ extern "C" int bcp_pq_check_stripes_async(bcp_queue *q, const bcp_stripe *stripe
   int rc = set_device(q->eng);
   if (rc) return rc;
   return submit_pq(q, stripes, nstripes, sources, nsources, q_body, nullptr, results_dev);
+}
+
+// The same three over window replay (bcp.h): a stripe's window may be 0 or a
+// multiple of the largest tile.
+extern "C" int bcp_pq_stripes_win_async(bcp_queue *q, const bcp_stripe *stripes, uint32_t nstripes,
+                                        const bcp_source *sources, uint32_t nsources, const uint64_t *q_dst) {
+  if (!q || !stripes || !q_dst || (nsources && !sources)) return -EINVAL;
+  if (!nstripes) return 0;
+  int rc = set_device(q->eng);
+  if (rc) return rc;
+  return submit_pq(q, stripes, nstripes, sources, nsources, q_dst, nullptr, nullptr, true);
+}
+
+extern "C" int bcp_pq_recover_stripes_win_async(bcp_queue *q, const bcp_stripe *stripes, uint32_t nstripes,
+                                                const bcp_source *sources, uint32_t nsources,
+                                                const bcp_pq_lost *lost) {
+  if (!q || !stripes || !lost || (nsources && !sources)) return -EINVAL;
+  if (!nstripes) return 0;
+  int rc = set_device(q->eng);
+  if (rc) return rc;
+  return submit_pq(q, stripes, nstripes, sources, nsources, nullptr, lost, nullptr, true);
+}
+
+extern "C" int bcp_pq_check_stripes_win_async(bcp_queue *q, const bcp_stripe *stripes, uint32_t nstripes,
+                                              const bcp_source *sources, uint32_t nsources, const uint64_t *q_body,
+                                              bcp_pq_check_result *results_dev) {
+  if (!q || !stripes || !q_body || !results_dev || (nsources && !sources)) return -EINVAL;
+  if (!nstripes) return 0;
+  int rc = set_device(q->eng);
+  if (rc) return rc;
+  return submit_pq(q, stripes, nstripes, sources, nsources, q_body, nullptr, results_dev, true);
 }
 
 extern "C" int bcp_xor_strided_async(bcp_queue *q, void *dst, uint64_t dst_stride, const void *src,

@@ -278,7 +278,7 @@ struct RingArgs {
 
 // ---------------------------------------------------------------------------
 // P + Q parity (bcp_pq.hip; bcp_pq_stripes_async, bcp_pq_recover_stripes_async,
-// bcp_pq_check_stripes_async).
+// bcp_pq_check_stripes_async, and their _win namesakes further down).
 // One record per stripe and one per tile, both written by the host: the
 // sources of a run stay in the caller's position order (source k has
 // coefficient g^k), so nothing here is sorted.
@@ -313,6 +313,28 @@ hipError_t launch_pq(hipStream_t st, int grid, int vecs, bool solve, const PqBat
 // n records to {UINT64_MAX, 0, 0, 0}.
 hipError_t launch_pq_check_init(hipStream_t st, bcp_pq_check_result *res, uint32_t n);
 hipError_t launch_pq_check(hipStream_t st, int grid, int vecs, const PqBatch &b, bcp_pq_check_result *res);
+
+// The windowed forms (bcp_pq_*_win_async): a batch in which some stripe has a
+// window W (a multiple of kPqWindowUnit, so a tile lies in one window and the
+// remap is per tile, not per lane).  Two more tables, staged behind the tiles,
+// keep every division on the host: per staged source where its replay starts
+// and what it replays, and per tile its offset in its own window.
+constexpr uint64_t kPqWindowUnit = 32768;  // the largest tile: desc_tile_bytes(8)
+struct PqWin {
+    uint64_t base;          // lw * W, lw = (len - 1) / W: the last readable window
+    uint64_t lim;           // (lw + 1) * W: stripe offsets from here on replay it
+};                          // no window, or len 0: {0, UINT64_MAX}
+struct PqWinTab {
+    const PqWin *win;       // beside PqBatch.sources
+    const uint64_t *offw;   // [ntiles]: (sub * T) mod W; 0 where the stripe has no window
+};
+struct PqBatchWin {
+    PqBatch b;
+    PqWinTab w;
+};
+// form 0 GEN, 1 SOLVE, 2 CHECK (res required for CHECK only); accounting as launch_pq.
+hipError_t launch_pq_win(hipStream_t st, int grid, int vecs, int form, const PqBatchWin &b,
+                         bcp_pq_check_result *res);
 
 // Kernel launchers (bcp_kernels.hip).  All return hipError_t.
 // Streaming fold.  Consumes ceil(ntiles / grab) + grid counts of a.ctr; the

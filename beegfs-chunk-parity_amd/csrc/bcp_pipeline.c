@@ -48,7 +48,10 @@
  * <root>/st<q>/parityq/<path>, same header), or the second chunk of a rebuild
  * from P and Q.  Those tasks' stripes go in a launch of their own per batch
  * (bcp_pq_stripes_async / bcp_pq_recover_stripes_async, sources in holder
- * order) beside the batch's bcp_xor_stripes_async.
+ * order) beside the batch's bcp_xor_stripes_async.  An item past the window
+ * has no Q unless bcp_pipeline_set_q_windowed is on; then its stripe carries
+ * the window and the launch is the _win entry point's (Q over the replayed
+ * streams, the P body still the reference's).
  */
 #define _GNU_SOURCE
 #include <errno.h>
@@ -315,6 +318,7 @@ typedef struct {
     task *t;
     latch *done;
     int corrupt_fd;                      /* rebuild: corrupt list (or -1) */
+    int q_win;                           /* windowed items have Q too (bcp_pipeline_set_q_windowed) */
 } stat_arg;
 
 typedef struct {
@@ -457,7 +461,7 @@ static void do_stat(job *p)
         if (t->vq && t->status == VERIFY_PENDING) {
             /* the Q state: by rule none, or a file in order beside P's */
             t->q_state = BCP_QSTATE_NONE;
-            if (t->q_st >= 0 && t->max_cs <= WINDOW) {
+            if (t->q_st >= 0 && (t->max_cs <= WINDOW || a->q_win)) {
                 uint64_t hq[MAX_STORAGE_TARGETS] = {0};
                 uint64_t qsize = 0;
                 int qhave = 0;
@@ -518,7 +522,7 @@ static void do_stat(job *p)
         for (int j = 0; j < w; j++)
             if (t->header[j] > t->max_cs)
                 t->max_cs = t->header[j];
-        ok = ok && t->max_cs <= WINDOW; /* windowed items have no Q */
+        ok = ok && (t->max_cs <= WINDOW || a->q_win); /* windowed items have no Q without the switch */
         for (int k = 0; k < t->n; k++) {
             struct stat st;
             if (k == t->parity_src || k == t->q_src) {
@@ -551,7 +555,7 @@ static void do_stat(job *p)
                 t->max_cs = t->size[k];
         }
         t->out_len = t->max_cs;
-        if (t->q_st >= 0 && t->max_cs > WINDOW) {
+        if (t->q_st >= 0 && t->max_cs > WINDOW && !a->q_win) {
             /* windowed: P only; a Q file from an earlier, smaller state goes */
             chunk_file(fn, sizeof(fn), a->root, t->q_st, "parityq", t->path);
             unlink(fn);
@@ -878,6 +882,7 @@ struct bcp_pipeline {
     bcp_pq_lost *lost;
     size_t desc_cap;    /* stripes the descriptor arrays hold */
     int q_on;           /* bcp_pipeline_set_q_parity */
+    int q_win;          /* bcp_pipeline_set_q_windowed */
     uint64_t q_written, q_no_target, q_windowed; /* of the last run */
     uint8_t *r2_unrec;  /* during a rebuild2 run: per item, 1 = unrecoverable after the stat phase */
     bcp_pipeline_timing last; /* of the last run */
@@ -1278,7 +1283,9 @@ static int pipeline_exec(bcp_pipeline *pl, const char *store_root, task *tasks, 
             return -ENOMEM;
         }
         for (size_t i = 0; i < nt; i++) {
-            args[i] = (stat_arg){{0}, store_root, &tasks[i], &l, corrupt_fd};
+            /* a run writes Q only with Q on; rebuild2 and verify_q read what is there */
+            const int q_win = pl->q_win && (pl->q_on || tasks[i].rebuild || tasks[i].verify);
+            args[i] = (stat_arg){{0}, store_root, &tasks[i], &l, corrupt_fd, q_win};
             pool_push(&pl->io, &args[i].j, do_stat);
         }
         latch_wait(&l);
@@ -1532,6 +1539,7 @@ static int pipeline_exec(bcp_pipeline *pl, const char *store_root, task *tasks, 
         uint64_t out_used = 0;
         long nwrites = 0;
         int recover = 0;
+        int win2 = 0; /* a windowed stripe among the P + Q ones: the _win entry points */
         /* verify with Q: the batch's syndrome records first, then the P check's */
         uint64_t nchk = 0;
         for (size_t i = first; i < last && qres; i++)
@@ -1544,7 +1552,9 @@ static int pipeline_exec(bcp_pipeline *pl, const char *store_root, task *tasks, 
                  * read), the sources the chunks in holder order */
                 const int nfold = t->parity_src;
                 t->out_off = (uint64_t)ns2 * sizeof(bcp_pq_check_result);
-                pl->st2[ns2] = (bcp_stripe){(uint64_t)S->d_in + data_off(t, nfold, dir), t->out_len, nsrc2, (uint32_t)nfold, 0};
+                pl->st2[ns2] = (bcp_stripe){(uint64_t)S->d_in + data_off(t, nfold, dir), t->out_len, nsrc2, (uint32_t)nfold,
+                                            t->max_cs > WINDOW ? WINDOW : 0};
+                win2 |= t->max_cs > WINDOW;
                 pl->qd[ns2] = (uint64_t)S->d_in + data_off(t, t->q_src, dir);
                 for (int k = 0; k < nfold; k++)
                     pl->so2[nsrc2++] = (bcp_source){(uint64_t)S->d_in + data_off(t, k, dir), t->size[k]};
@@ -1571,7 +1581,8 @@ static int pipeline_exec(bcp_pipeline *pl, const char *store_root, task *tasks, 
                 l->len_x = t->out_len;
                 l->dst_y = (uint64_t)S->d_out + out_off2(t);
                 l->len_y = t->out_len2;
-                pl->st2[ns2] = (bcp_stripe){0, t->max_cs, nsrc2, (uint32_t)t->width, 0};
+                pl->st2[ns2] = (bcp_stripe){0, t->max_cs, nsrc2, (uint32_t)t->width, t->max_cs > WINDOW ? WINDOW : 0};
+                win2 |= t->max_cs > WINDOW;
                 for (int j = 0; j < t->width; j++)
                     pl->so2[nsrc2 + j] = (bcp_source){0, 0};
                 for (int k = 0; k < t->n; k++)
@@ -1585,7 +1596,9 @@ static int pipeline_exec(bcp_pipeline *pl, const char *store_root, task *tasks, 
             }
             if (t->has2) {
                 /* gen with a Q file: P and Q in one pass, sources in holder order */
-                pl->st2[ns2] = (bcp_stripe){(uint64_t)S->d_out + t->out_off, t->out_len, nsrc2, (uint32_t)t->n, 0};
+                pl->st2[ns2] = (bcp_stripe){(uint64_t)S->d_out + t->out_off, t->out_len, nsrc2, (uint32_t)t->n,
+                                            t->max_cs > WINDOW ? WINDOW : 0};
+                win2 |= t->max_cs > WINDOW;
                 pl->qd[ns2] = (uint64_t)S->d_out + out_off2(t);
                 for (int k = 0; k < t->n; k++)
                     pl->so2[nsrc2++] = (bcp_source){(uint64_t)S->d_in + data_off(t, k, dir), t->size[k]};
@@ -1612,10 +1625,16 @@ static int pipeline_exec(bcp_pipeline *pl, const char *store_root, task *tasks, 
                                                    (bcp_check_result *)((uint8_t *)S->d_out +
                                                                         nchk * sizeof(bcp_pq_check_result)))
                          : bcp_xor_stripes_async(L->qk, st, ns, so, nsrc)) ||
-            (ns2 && (rc = qres      ? bcp_pq_check_stripes_async(L->qk, pl->st2, ns2, pl->so2, nsrc2, pl->qd,
-                                                                 (bcp_pq_check_result *)S->d_out)
-                          : recover ? bcp_pq_recover_stripes_async(L->qk, pl->st2, ns2, pl->so2, nsrc2, pl->lost)
-                                    : bcp_pq_stripes_async(L->qk, pl->st2, ns2, pl->so2, nsrc2, pl->qd))) ||
+            (ns2 && !win2 &&
+             (rc = qres      ? bcp_pq_check_stripes_async(L->qk, pl->st2, ns2, pl->so2, nsrc2, pl->qd,
+                                                          (bcp_pq_check_result *)S->d_out)
+                   : recover ? bcp_pq_recover_stripes_async(L->qk, pl->st2, ns2, pl->so2, nsrc2, pl->lost)
+                             : bcp_pq_stripes_async(L->qk, pl->st2, ns2, pl->so2, nsrc2, pl->qd))) ||
+            (ns2 && win2 &&
+             (rc = qres      ? bcp_pq_check_stripes_win_async(L->qk, pl->st2, ns2, pl->so2, nsrc2, pl->qd,
+                                                              (bcp_pq_check_result *)S->d_out)
+                   : recover ? bcp_pq_recover_stripes_win_async(L->qk, pl->st2, ns2, pl->so2, nsrc2, pl->lost)
+                             : bcp_pq_stripes_win_async(L->qk, pl->st2, ns2, pl->so2, nsrc2, pl->qd))) ||
             (rc = bcp_event_record(S->ev_k, L->qk)) ||
             (rc = bcp_queue_wait_event(L->qd, S->ev_k)) ||
             (rc = bcp_d2h_async(L->qd, S->h_out, S->d_out, (size_t)out_used)) ||
@@ -2015,6 +2034,14 @@ int bcp_pipeline_set_q_parity(bcp_pipeline *pl, int on)
     if (!pl || (on != 0 && on != 1))
         return -EINVAL;
     pl->q_on = on;
+    return 0;
+}
+
+int bcp_pipeline_set_q_windowed(bcp_pipeline *pl, int on)
+{
+    if (!pl || (on != 0 && on != 1))
+        return -EINVAL;
+    pl->q_win = on;
     return 0;
 }
 

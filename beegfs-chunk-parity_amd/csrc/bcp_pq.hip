@@ -23,6 +23,11 @@
 //          position k with g^k * Ps = Qs -- and commits first offset, counts
 //          and member mask to the stripe's record (bcp_pq_check_result).
 //
+// Each form also exists over window replay (pq_win_desc, the _win entry
+// points): D_k is then the reference's replayed stream R_k of source k (bcp.h),
+// which the kernel reads by remapping, per source and tile, the offset it loads
+// from (pq_eff_off); outputs and bodies are addressed as before.
+//
 // Schedule and load shape are the descriptor fold's (bcp_kernels.hip): a
 // device-wide atomicAdd-fed tile queue, wave-contiguous lanes, 16-byte
 // non-temporal loads, every load of a group of four sources issued before its
@@ -41,41 +46,62 @@ __device__ __forceinline__ v4u mul2(v4u x) {
   return ((x << 1) & 0xfefefefeu) ^ (((m << 1) - (m >> 7)) & 0x1d1d1d1du);
 }
 
+// Window replay (the _win entry points): where source k's bytes for the tile at
+// stripe offset `off` lie in the source.  Below lim = (lw_k + 1) * W the
+// stream is the source itself (zero padded); from there on it replays the
+// last readable window, base = lw_k * W, at the tile's offset in its own
+// window, offw = off mod W.  Both records are the host's (PqWin, PqBatchWin);
+// a source without replay has lim = UINT64_MAX.  Wave-uniform.
+__device__ __forceinline__ uint64_t pq_eff_off(const_as<PqWin> *w, uint64_t off, uint64_t offw) {
+  return off < w->lim ? off : w->base + offw;
+}
+
 // G consecutive sources run[0 .. G) of a stripe, folded highest position
 // first: q = 2*q ^ D, p ^= D.  Every load of the group goes out before the
 // arithmetic.
-template <int G, int U>
-__device__ __forceinline__ void pq_group(v4u (&p)[U], v4u (&q)[U], const_as<bcp_source> *run, uint64_t off,
-                                         uint32_t T, uint32_t lane_off) {
-  uint64_t ptr[G], len[G];
+//
+// WIN: source i is read at its effective offset eo(i) (pq_eff_off), the place
+// the window replay takes this tile's bytes from; everything below that is
+// `off` in the plain form -- covering test, loads, tail, miss -- is eo(i).
+template <int G, int U, bool WIN>
+__device__ __forceinline__ void pq_group(v4u (&p)[U], v4u (&q)[U], const_as<bcp_source> *run,
+                                         const_as<PqWin> *wrun, uint64_t off, uint64_t offw, uint32_t T,
+                                         uint32_t lane_off) {
+  uint64_t ptr[G], len[G], weo[G];
+  // (the plain form names `off` itself, so that its code is what it was before there was a windowed one)
+  auto eo = [&](int i) -> uint64_t {
+    if constexpr (WIN) return weo[i];
+    else return off;
+  };
   bool cover = true;
 #pragma unroll
   for (int i = 0; i < G; i++) {
     ptr[i] = run[i].ptr;
     len[i] = run[i].len;
-    cover = cover && len[i] >= off + T;
+    if constexpr (WIN) weo[i] = pq_eff_off(wrun + i, off, offw);
+    cover = cover && len[i] >= eo(i) + T;
   }
   v4u x[G][U];
   if (cover) {
 #pragma unroll
     for (int i = 0; i < G; i++) {
-      const glob<v4u_u> *s = gp<const v4u_u>(ptr[i] + off + lane_off);
+      const glob<v4u_u> *s = gp<const v4u_u>(ptr[i] + eo(i) + lane_off);
 #pragma unroll
       for (int u = 0; u < U; u++) x[i][u] = __builtin_nontemporal_load(s + u * 64);
     }
   } else {
 #pragma unroll
     for (int i = 0; i < G; i++) {
-      if (len[i] >= off + T) {
-        const glob<v4u_u> *s = gp<const v4u_u>(ptr[i] + off + lane_off);
+      if (len[i] >= eo(i) + T) {
+        const glob<v4u_u> *s = gp<const v4u_u>(ptr[i] + eo(i) + lane_off);
 #pragma unroll
         for (int u = 0; u < U; u++) x[i][u] = __builtin_nontemporal_load(s + u * 64);
-      } else if (len[i] <= off) {  // zero padding (also a (0, 0) source: never dereferenced)
+      } else if (len[i] <= eo(i)) {  // zero padding (also a (0, 0) source: never dereferenced)
 #pragma unroll
         for (int u = 0; u < U; u++) x[i][u] = zero4();  // (never read: the 2*q step below)
       } else {
-        gbyte *s = gp<const unsigned char>(ptr[i] + off);
-        const uint64_t left = len[i] - off;  // < T: the source ends inside the tile
+        gbyte *s = gp<const unsigned char>(ptr[i] + eo(i));
+        const uint64_t left = len[i] - eo(i);  // < T: the source ends inside the tile
 #pragma unroll
         for (int u = 0; u < U; u++) x[i][u] = load_src_tail(s, left, lane_off + u * 1024u);
       }
@@ -83,7 +109,7 @@ __device__ __forceinline__ void pq_group(v4u (&p)[U], v4u (&q)[U], const_as<bcp_
     // a source that misses the tile is a 2*q step only (uniform branch)
 #pragma unroll
     for (int i = G - 1; i >= 0; i--) {
-      if (len[i] <= off) {
+      if (len[i] <= eo(i)) {
 #pragma unroll
         for (int u = 0; u < U; u++) q[u] = mul2(q[u]);
       } else {
@@ -222,14 +248,24 @@ __device__ __forceinline__ void pq_check_commit(bcp_pq_check_result *rec, const 
 
 enum PqForm { kPqGen = 0, kPqSolve = 1, kPqCheck = 2 };
 
-template <int U, PqForm F>
-__device__ __forceinline__ void pq_tile(const PqBatch &b, uint32_t t, bcp_pq_check_result *res) {
+// WIN: the windowed instantiations (PqBatchWin's two more tables, w); a stripe
+// without a window in such a batch has lim = UINT64_MAX on every source and
+// so keeps the plain semantics.  The bodies and the outputs are addressed
+// with plain `off` in both.
+template <int U, PqForm F, bool WIN>
+__device__ __forceinline__ void pq_tile(const PqBatch &b, const PqWinTab &w, uint32_t t, bcp_pq_check_result *res) {
   constexpr bool SOLVE = F == kPqSolve;
   constexpr uint32_t T = (uint32_t)kBlock * U * 16u;
   const_as<PqTile> *tr = cst(b.tiles) + t;
   const_as<PqStripe> *d = cst(b.stripes) + tr->stripe;
   const uint64_t off = (uint64_t)tr->sub * T;
   const_as<bcp_source> *run = cst(b.sources) + d->first_src;
+  const_as<PqWin> *wrun = nullptr;  // per source, beside run
+  uint64_t offw = 0;                // off mod W of a windowed stripe
+  if constexpr (WIN) {
+    wrun = cst(w.win) + d->first_src;
+    offw = cst(w.offw)[t];
+  }
   // this lane's vector u = 0 inside the tile; vector u is at + u * 1024
   const uint32_t lane_off = ((threadIdx.x >> 6) * (64u * U) + (threadIdx.x & 63u)) * 16u;
   const uint64_t out_left = d->out_len - off;  // > 0: the host cuts tiles below out_len only
@@ -261,15 +297,19 @@ __device__ __forceinline__ void pq_tile(const PqBatch &b, uint32_t t, bcp_pq_che
   }
   uint32_t k = d->nsrc;
   // the highest positions that miss the tile: q is still zero there, nothing to do
-  while (k > 0 && run[k - 1].len <= off) k--;
+  if constexpr (WIN) {
+    while (k > 0 && run[k - 1].len <= pq_eff_off(wrun + (k - 1), off, offw)) k--;
+  } else {
+    while (k > 0 && run[k - 1].len <= off) k--;
+  }
   while (k >= 4) {
     k -= 4;
-    pq_group<4, U>(p, q, run + k, off, T, lane_off);
+    pq_group<4, U, WIN>(p, q, run + k, wrun + k, off, offw, T, lane_off);
   }
   switch (k) {
-    case 3: pq_group<3, U>(p, q, run, off, T, lane_off); break;
-    case 2: pq_group<2, U>(p, q, run, off, T, lane_off); break;
-    case 1: pq_group<1, U>(p, q, run, off, T, lane_off); break;
+    case 3: pq_group<3, U, WIN>(p, q, run, wrun, off, offw, T, lane_off); break;
+    case 2: pq_group<2, U, WIN>(p, q, run, wrun, off, offw, T, lane_off); break;
+    case 1: pq_group<1, U, WIN>(p, q, run, wrun, off, offw, T, lane_off); break;
     default: break;
   }
   if constexpr (F == kPqCheck) {
@@ -306,8 +346,8 @@ __device__ __forceinline__ void pq_tile(const PqBatch &b, uint32_t t, bcp_pq_che
   }
 }
 
-template <int U, PqForm F>
-__device__ __forceinline__ void pq_body(const PqBatch &b, bcp_pq_check_result *res) {
+template <int U, PqForm F, bool WIN = false>
+__device__ __forceinline__ void pq_body(const PqBatch &b, bcp_pq_check_result *res, const PqWinTab &w = PqWinTab{}) {
   // Work queue, one tile per grab (two LDS slots as in stream_body).
   __shared__ uint32_t next[2];
   if (threadIdx.x == 0) next[0] = queue_grab(b.ctr, b.base);
@@ -315,7 +355,7 @@ __device__ __forceinline__ void pq_body(const PqBatch &b, bcp_pq_check_result *r
   uint32_t t = __builtin_amdgcn_readfirstlane(next[0]);
   int slot = 0;
   while (t < b.ntiles) {
-    pq_tile<U, F>(b, t, res);
+    pq_tile<U, F, WIN>(b, w, t, res);
     slot ^= 1;
     if (threadIdx.x == 0) next[slot] = queue_grab(b.ctr, b.base);
     __syncthreads();
@@ -335,6 +375,13 @@ __global__ __launch_bounds__(kBlock) void pq_check_desc(PqBatch b, bcp_pq_check_
   pq_body<U, kPqCheck>(b, res);
 }
 
+// The windowed forms of all three (the _win entry points): one kernel per
+// tile size and form, the form a template argument as above.
+template <int U, int F>
+__global__ __launch_bounds__(kBlock) void pq_win_desc(PqBatchWin b, bcp_pq_check_result *res) {
+  pq_body<U, (PqForm)F, true>(b.b, res, b.w);
+}
+
 __global__ __launch_bounds__(kBlock) void pq_check_init(bcp_pq_check_result *res, uint32_t n) {
   const uint32_t i = blockIdx.x * kBlock + threadIdx.x;
   if (i < n) res[i] = bcp_pq_check_result{~0ull, 0ull, 0ull, 0ull};
@@ -348,6 +395,22 @@ hipError_t launch_pq(hipStream_t st, int grid, int vecs, bool solve, const PqBat
   } else {
     if (solve) hipLaunchKernelGGL((pq_desc<4, true>), dim3(grid), dim3(kBlock), 0, st, b);
     else hipLaunchKernelGGL((pq_desc<4, false>), dim3(grid), dim3(kBlock), 0, st, b);
+  }
+  return hipGetLastError();
+}
+
+hipError_t launch_pq_win(hipStream_t st, int grid, int vecs, int form, const PqBatchWin &b, bcp_pq_check_result *res) {
+  if (grid <= 0 || !pq_vecs_ok(vecs) || form < 0 || form > 2 || (form == kPqCheck) != (res != nullptr))
+    return hipErrorInvalidValue;
+  const dim3 g(grid), bl(kBlock);
+  if (vecs == 8) {
+    if (form == kPqGen) hipLaunchKernelGGL((pq_win_desc<8, kPqGen>), g, bl, 0, st, b, res);
+    else if (form == kPqSolve) hipLaunchKernelGGL((pq_win_desc<8, kPqSolve>), g, bl, 0, st, b, res);
+    else hipLaunchKernelGGL((pq_win_desc<8, kPqCheck>), g, bl, 0, st, b, res);
+  } else {
+    if (form == kPqGen) hipLaunchKernelGGL((pq_win_desc<4, kPqGen>), g, bl, 0, st, b, res);
+    else if (form == kPqSolve) hipLaunchKernelGGL((pq_win_desc<4, kPqSolve>), g, bl, 0, st, b, res);
+    else hipLaunchKernelGGL((pq_win_desc<4, kPqCheck>), g, bl, 0, st, b, res);
   }
   return hipGetLastError();
 }

@@ -6,7 +6,8 @@
  *   bcp find-all-chunks <chunks_dir>
  *       bp-find-all-chunks: the record stream on stdout.
  *   bcp parity-gen --complete|--partial [--pipeline|--protocol|--procs] [--fold MODE]
- *                  [--read PATH] [--lanes N] [--force] [--changelog DIR] [--q] <store_root> <ntargets>
+ *                  [--read PATH] [--lanes N] [--force] [--changelog DIR] [--q] [--q-windowed]
+ *                  <store_root> <ntargets>
  *       beegfs-parity-gen + bp-parity-gen (src/beegfs-parity-gen:1-135,
  *       gen/main.c): target bookkeeping, phase 1 from a scan of every
  *       target (--complete) or from record files DIR/st<k> (--partial,
@@ -28,16 +29,20 @@
  *       :94-108, :120-126).  On success <root>/last-gen-timestamp.
  *       --q (pipeline only; usage with --protocol / --procs): also write the Q
  *       parity files <root>/st<q>/parityq/<path> (bcp_pipeline_set_q_parity).
+ *       --q-windowed (implies --q): also for items past the 10 MiB window
+ *       (bcp_pipeline_set_q_windowed).  A --q run without it removes those
+ *       items' Q files, so a store that uses it uses it in every run.
  *   bcp parity-rebuild [--pipeline|--protocol|--procs] [--fold MODE] [--read PATH] [--lanes N]
- *                      [--db DIR] [--corrupt FILE] [--also TARGET] [--lost FILE]
+ *                      [--db DIR] [--corrupt FILE] [--also TARGET] [--lost FILE] [--q-windowed]
  *                      <store_root> <ntargets> <target>
  *       beegfs-parity-rebuild + bp-parity-rebuild (rebuild/main.c), through
  *       the batched pipeline (default), the per-rank protocol (--protocol)
  *       or rank processes (--procs).  --also TARGET (pipeline only): a second
  *       target is lost too; chunks are rebuilt from P, from Q or from both
  *       (bcp_pipeline_rebuild2), the paths that cannot be go to --lost FILE and
- *       the exit status is then 1.
- *   bcp parity-verify [--db DIR] [--bad FILE] [--read PATH] [--q [--culprits FILE]]
+ *       the exit status is then 1.  --q-windowed (with --also): items past the
+ *       window have Q files too and are recovered like the others.
+ *   bcp parity-verify [--db DIR] [--bad FILE] [--read PATH] [--q [--culprits FILE] [--q-windowed]]
  *                     <store_root> <ntargets>
  *       The scrub (no counterpart in the reference): for every item of the
  *       database (default <root>/st0/db) the batched pipeline reads the chunks
@@ -53,7 +58,8 @@
  *       second summary line has the Q states and the culprits; --culprits FILE
  *       gets one line "path<TAB>data|p|q|many<TAB>target" per mismatch; --bad
  *       also lists the items whose Q file is missing or out of order, and
- *       those make the exit status 1 too.
+ *       those make the exit status 1 too.  --q-windowed (with --q): items
+ *       past the window are expected to have a Q file and are checked with it.
  *
  * Items whose path would leave the store (absolute, "..") are skipped and
  * counted as refused; a run with refused items exits 1.
@@ -76,11 +82,11 @@ static int usage(void)
 {
     fputs("usage: bcp find-all-chunks <chunks_dir>\n"
           "       bcp parity-gen --complete|--partial [--pipeline|--protocol|--procs] [--fold MODE] [--read PATH]\n"
-          "                      [--lanes N] [--force] [--changelog DIR] [--q] <store_root> <ntargets>\n"
+          "                      [--lanes N] [--force] [--changelog DIR] [--q] [--q-windowed] <store_root> <ntargets>\n"
           "       bcp parity-rebuild [--pipeline|--protocol|--procs] [--fold MODE] [--read PATH] [--lanes N]\n"
-          "                          [--db DIR] [--corrupt FILE] [--also TARGET] [--lost FILE]\n"
+          "                          [--db DIR] [--corrupt FILE] [--also TARGET] [--lost FILE] [--q-windowed]\n"
           "                          <store_root> <ntargets> <target>\n"
-          "       bcp parity-verify [--db DIR] [--bad FILE] [--read PATH] [--q [--culprits FILE]]\n"
+          "       bcp parity-verify [--db DIR] [--bad FILE] [--read PATH] [--q [--culprits FILE] [--q-windowed]]\n"
           "                         <store_root> <ntargets>\n"
           "       engine: --pipeline (default: batched pipeline on every GPU) | --protocol (per-rank\n"
           "               process_task, ranks as threads) | --procs (ranks as processes)\n"
@@ -91,7 +97,9 @@ static int usage(void)
           "       --q (also write Q parity files) and --also TARGET (a second lost target; --lost FILE lists\n"
           "            what cannot be rebuilt) apply to the pipeline only\n"
           "       parity-verify --q also reads and checks the Q files and names the wrong file of a mismatch;\n"
-          "            --culprits FILE (with --q only) lists path, data|p|q|many and the storage target\n",
+          "            --culprits FILE (with --q only) lists path, data|p|q|many and the storage target\n"
+          "       --q-windowed (pipeline only): Q files for items past the 10 MiB window too; parity-gen (implies\n"
+          "            --q; a --q run without it removes those Q files), parity-rebuild --also, parity-verify --q\n",
           stderr);
     return 1;
 }
@@ -203,7 +211,7 @@ static int cmd_gen(int argc, char **argv)
 {
     const double t_start = now_s();
     int complete = -1, engines = 0, use_pipeline = 1, use_procs = 0, lanes = 12, force = 0, read_arg = 0, fold_arg = 0;
-    int q_parity = 0;
+    int q_parity = 0, q_windowed = 0;
     const char *changelog = NULL;
     int i = 0;
     for (; i < argc && argv[i][0] == '-'; i++) {
@@ -231,6 +239,8 @@ static int cmd_gen(int argc, char **argv)
             force = 1;
         else if (!strcmp(argv[i], "--q"))
             q_parity = 1;
+        else if (!strcmp(argv[i], "--q-windowed"))
+            q_parity = q_windowed = 1;
         else if (!strcmp(argv[i], "--lanes") && i + 1 < argc)
             lanes = atoi(argv[++i]);
         else if (!strcmp(argv[i], "--changelog") && i + 1 < argc)
@@ -307,6 +317,8 @@ static int cmd_gen(int argc, char **argv)
         t_setup = now_s();
         if (!rc && q_parity)
             rc = bcp_pipeline_set_q_parity(pl, 1);
+        if (!rc && q_windowed)
+            rc = bcp_pipeline_set_q_windowed(pl, 1);
         if (!rc)
             rc = bcp_gen_round_pipeline(pl, root, ntargets, es, NULL, stderr, &st, &planned);
         if (pl)
@@ -347,6 +359,7 @@ static int cmd_rebuild(int argc, char **argv)
 {
     const char *db = NULL, *corrupt = NULL, *lost = NULL;
     int engines = 0, use_pipeline = 1, use_procs = 0, read_arg = 0, fold_arg = 0, also = -1, also_arg = 0;
+    int q_windowed = 0;
     int i = 0;
     for (; i < argc && argv[i][0] == '-'; i++) {
         if (!strcmp(argv[i], "--db") && i + 1 < argc)
@@ -361,7 +374,9 @@ static int cmd_rebuild(int argc, char **argv)
             if (!*argv[i] || *end || also < 0)
                 return usage();
             also_arg = 1;
-        } else if (!strcmp(argv[i], "--pipeline"))
+        } else if (!strcmp(argv[i], "--q-windowed"))
+            q_windowed = 1;
+        else if (!strcmp(argv[i], "--pipeline"))
             engines++, use_pipeline = 1;
         else if (!strcmp(argv[i], "--protocol"))
             engines++, use_pipeline = 0;
@@ -385,7 +400,7 @@ static int cmd_rebuild(int argc, char **argv)
         return usage();
     const char *root = argv[i];
     const int ntargets = atoi(argv[i + 1]), target = atoi(argv[i + 2]);
-    if ((also_arg || lost) && (!use_pipeline || !also_arg || also == target || also >= ntargets))
+    if ((also_arg || lost || q_windowed) && (!use_pipeline || !also_arg || also == target || also >= ntargets))
         return usage();
     bcp_run_stats st;
     bcp_rebuild2_stats st2;
@@ -417,6 +432,8 @@ static int cmd_rebuild(int argc, char **argv)
         } else if (!rc) {
             bcp_pipeline *pl = NULL;
             rc = pipeline_on_all_gpus(&pl, 0);
+            if (!rc && q_windowed)
+                rc = bcp_pipeline_set_q_windowed(pl, 1);
             if (!rc)
                 rc = also_arg ? bcp_pipeline_rebuild2(pl, root, ntargets, target, also, items, n, corrupt, lost, stderr,
                                                       &st, &st2)
@@ -446,7 +463,7 @@ static int cmd_rebuild(int argc, char **argv)
 static int cmd_verify(int argc, char **argv)
 {
     const char *db = NULL, *bad = NULL, *culprits = NULL;
-    int i = 0, with_q = 0;
+    int i = 0, with_q = 0, q_windowed = 0;
     for (; i < argc && argv[i][0] == '-'; i++) {
         if (!strcmp(argv[i], "--db") && i + 1 < argc)
             db = argv[++i];
@@ -456,13 +473,15 @@ static int cmd_verify(int argc, char **argv)
             culprits = argv[++i];
         else if (!strcmp(argv[i], "--q"))
             with_q = 1;
+        else if (!strcmp(argv[i], "--q-windowed"))
+            q_windowed = 1;
         else if (!strcmp(argv[i], "--read") && i + 1 < argc) {
             if ((g_read_mode = read_mode_arg(argv[++i])) < 0)
                 return usage();
         } else
             return usage();
     }
-    if (argc - i != 2 || (culprits && !with_q))
+    if (argc - i != 2 || ((culprits || q_windowed) && !with_q))
         return usage();
     const char *root = argv[i];
     const int ntargets = atoi(argv[i + 1]);
@@ -491,6 +510,8 @@ static int cmd_verify(int argc, char **argv)
     if (!rc) {
         bcp_pipeline *pl = NULL;
         rc = pipeline_on_all_gpus(&pl, 0);
+        if (!rc && q_windowed)
+            rc = bcp_pipeline_set_q_windowed(pl, 1);
         if (!rc && with_q) {
             rc = bcp_pipeline_verify_q(pl, root, ntargets, items, n, NULL, bad, culprits, stderr, &qs);
             vs = qs.v;

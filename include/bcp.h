@@ -51,7 +51,9 @@ extern "C" {
  * bcp_pq_lost / bcp_q_target, the "last_desc_form" values 4 and 5 and the
  * option "pq_blocks_per_cu"; the Q-aware scrub's
  * bcp_pq_check_stripes_async / bcp_pq_check_result / bcp_pq_culprit and the
- * "last_desc_form" value 6.
+ * "last_desc_form" value 6; Q parity over window replay,
+ * bcp_pq_stripes_win_async / bcp_pq_recover_stripes_win_async /
+ * bcp_pq_check_stripes_win_async and the "last_desc_form" values 7, 8 and 9.
  * 3 (r05): the pipeline's MAP read mode (BCP_READ_MAP), its
  * bcp_pipeline_timing fields and bcp_host_register_dma_src removed.
  * 2 (r04): bcp_task.h's bcp_run_stats gained `refused`, bcp_pipeline_opts
@@ -194,7 +196,10 @@ int bcp_check_stripes_async(bcp_queue *q, const bcp_stripe *stripes,
  * k = 0 .. nsrc-1, each zero-padded to out_len as above:
  *   P[j] = XOR_k D_k[j]        Q[j] = XOR_k g^k * D_k[j]      0 <= j < out_len
  * There is no window replay here (a replayed P is not the plain XOR, which
- * the two-loss algebra needs): window != 0 is -EINVAL. */
+ * the two-loss algebra needs): window != 0 is -EINVAL.  This holds for
+ * bcp_pq_stripes_async, bcp_pq_recover_stripes_async and
+ * bcp_pq_check_stripes_async; their _win namesakes further down define both
+ * parities over the replayed streams instead. */
 /* P and Q of every stripe.  stripes[s].dst = P body (0: P is not written),
  * q_dst[s] = Q body (required); both out_len bytes.  Source k of the stripe's
  * run has coefficient g^k (position order is kept); window must be 0. */
@@ -243,6 +248,36 @@ typedef struct bcp_pq_check_result {
 int bcp_pq_check_stripes_async(bcp_queue *q, const bcp_stripe *stripes, uint32_t nstripes,
                                const bcp_source *sources, uint32_t nsources,
                                const uint64_t *q_body, bcp_pq_check_result *results_dev);
+/* ---- P + Q over window replay ------------------------------------------ */
+/* The three entry points above for stripes with a window W.  The replayed
+ * stream of source k (quirk A3-q1, see the top of this file) is a function of
+ * that source alone: with D_k' = D_k zero-padded and lw_k = (len_k - 1) / W,
+ *   R_k[j] = D_k'[j]                     for j <  (lw_k + 1) * W
+ *   R_k[j] = D_k'[lw_k * W + j mod W]    for j >= (lw_k + 1) * W
+ *   R_k    = 0 everywhere                for len_k = 0
+ * and, for 0 <= j < out_len,
+ *   P[j] = XOR_k R_k[j]        Q[j] = XOR_k g^k * R_k[j].
+ * P is what bcp_xor_stripes_async writes for the same stripe when out_len is
+ * the longest len_k, the reference's parity body.  The whole algebra above
+ * holds over the R_k: the syndromes over the survivors' replayed streams give
+ * R_x and R_y, and the first len_x bytes of R_x are D_x.  Survivors replay to
+ * out_len whether or not the longest member is among them.
+ * Signatures, validation and results are the namesakes', except that
+ * stripes[s].window may be 0 (that stripe: R_k = D_k', exactly the namesake's
+ * semantics) or a non-zero multiple of 32768; any other window is -EINVAL.  A
+ * batch may mix windows. */
+int bcp_pq_stripes_win_async(bcp_queue *q, const bcp_stripe *stripes, uint32_t nstripes,
+                             const bcp_source *sources, uint32_t nsources, const uint64_t *q_dst);
+int bcp_pq_recover_stripes_win_async(bcp_queue *q, const bcp_stripe *stripes, uint32_t nstripes,
+                                     const bcp_source *sources, uint32_t nsources, const bcp_pq_lost *lost);
+/* The record is bcp_pq_check_result unchanged, with Ps = P ^ XOR_k R_k and
+ * Qs = Q ^ XOR_k g^k * R_k: first_bad, p_bad and q_bad are offsets and counts
+ * in the replayed streams, so one wrong byte of D_k counts once for every place
+ * below out_len it is replayed to, and names position k at each of them. */
+int bcp_pq_check_stripes_win_async(bcp_queue *q, const bcp_stripe *stripes, uint32_t nstripes,
+                                   const bcp_source *sources, uint32_t nsources,
+                                   const uint64_t *q_body, bcp_pq_check_result *results_dev);
+
 /* Which single member a record blames (pure host arithmetic, no device,
  * bcp_pq_host.c).  Returns the kind, or -EINVAL for a null record;
  * *position (may be null) is the data position for DATA, else -1. */
@@ -372,7 +407,9 @@ int bcp_set_option(bcp_engine *eng, const char *key, int value);
  * xor_desc, 2 = xor_desc_args, 3 = desc_tiles + the check kernel of
  * bcp_check_stripes_async, 4 = the P + Q kernel of bcp_pq_stripes_async,
  * 5 = its recovery form, bcp_pq_recover_stripes_async, 6 = its syndrome
- * form, bcp_pq_check_stripes_async). */
+ * form, bcp_pq_check_stripes_async, 7 / 8 / 9 = the windowed kernels of
+ * bcp_pq_stripes_win_async / bcp_pq_recover_stripes_win_async /
+ * bcp_pq_check_stripes_win_async, taken by a batch with a windowed stripe). */
 int bcp_get_option(bcp_engine *eng, const char *key, int *value);
 /* Timer slots for bcp_queue_mark / bcp_queue_elapsed_ms. */
 #define BCP_TIMER_SLOTS 64

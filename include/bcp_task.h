@@ -692,7 +692,8 @@ int bcp_pipeline_verify(bcp_pipeline *pl, const char *store_root, int ntargets, 
  * the Q state, from bcp_q_target, the header's maximum and a stat of
  * parityq/<path> (a Q file at a former Q target is never looked at): */
 #define BCP_QSTATE_CHECKED 0  /* Q body read and compared with P in one pass */
-#define BCP_QSTATE_NONE    1  /* no Q by rule: no Q target, or max(header) > BCP_WINDOW_BYTES */
+#define BCP_QSTATE_NONE    1  /* no Q by rule: no Q target, or max(header) > BCP_WINDOW_BYTES
+                                 (the latter not under bcp_pipeline_set_q_windowed) */
 #define BCP_QSTATE_BAD     2  /* should have Q: file missing, size != 8n + max(header), or its header != P's */
 /* A CHECKED item's chunks, P body and Q body (file offset 8n) are read;
  * NONE and BAD items go through bcp_check_stripes_async exactly as in
@@ -727,12 +728,30 @@ int bcp_pipeline_verify_q(bcp_pipeline *pl, const char *store_root, int ntargets
  * ascending target order has position j.  P files are byte-identical to a run
  * without Q.  An item gets no Q file when it has no Q target (every target is
  * a holder or P) or when max_cs > BCP_WINDOW_BYTES (windowed items: their P is
- * the reference's replayed stream, not the plain XOR); it is then protected by
+ * the reference's replayed stream, not the plain XOR; but see
+ * bcp_pipeline_set_q_windowed); it is then protected by
  * P only, and a Q file found at its Q target is unlinked.  An item without
  * holders unlinks both files.  Failed Q writes count in `errors`.  When an
  * item's holders change, its Q target may move: the old Q file is never read
  * again but is not removed.  Default 0: everything as without this call. */
 int bcp_pipeline_set_q_parity(bcp_pipeline *pl, int on);
+/* Q for windowed items too (0 or 1, anything else -EINVAL; default 0:
+ * everything as without this call).  With it on, max_cs > BCP_WINDOW_BYTES is
+ * no reason to go without Q:
+ *   run (needs Q on)  a windowed item with a Q target gets its Q file, the
+ *                     same header and max_cs bytes of Q over the replayed
+ *                     streams (bcp.h, bcp_pq_stripes_win_async, window
+ *                     BCP_WINDOW_BYTES); its P file is byte-identical to the
+ *                     one written without Q; it counts in q_stats' `written`,
+ *                     and `windowed` is 0;
+ *   rebuild2          windowed items are recovered by the rules of the others
+ *                     (one holder lost with P present stays the plain rebuild);
+ *   verify_q          a windowed item's Q state is CHECKED when its Q file is
+ *                     in order, else BAD, and a CHECKED one gets its culprit.
+ * A Q file of a windowed item is only usable with this switch on.  A run with
+ * Q on and this switch off unlinks the Q files of windowed items, as it
+ * always has: turn it on for every run over a store that uses it. */
+int bcp_pipeline_set_q_windowed(bcp_pipeline *pl, int on);
 /* Of the last run: Q files written, items left without one for lack of a Q
  * target, and windowed items.  Each pointer may be NULL. */
 int bcp_pipeline_q_stats(const bcp_pipeline *pl, uint64_t *written, uint64_t *no_target, uint64_t *windowed);
@@ -747,7 +766,7 @@ int bcp_pipeline_q_stats(const bcp_pipeline *pl, uint64_t *written, uint64_t *no
  * A needed P or Q file is usable when it exists with size 8n + max(header);
  * when both are used their headers must be equal.  An item that needs Q but
  * has none, whose needed file is not usable, or that is windowed and needs Q
- * is unrecoverable: nothing is written for it, its path goes to the lost list
+ * (without bcp_pipeline_set_q_windowed) is unrecoverable: nothing is written for it, its path goes to the lost list
  * (created and truncated like the corrupt list; item order), the run goes on
  * and returns 0.  Validation as bcp_pipeline_rebuild, and target_a !=
  * target_b.  stats and st2 may be NULL. */

@@ -23,10 +23,27 @@ written), (n + 1) x out_len for the fold.  Reported: ms, the fraction of the
 and 1..3 workgroups per CU (pq_blocks_per_cu); without it the engine's
 defaults run.
 
+--windowed times the windowed GEN kernel (bcp_pq_stripes_win_async, window
+10 MiB) instead, against the existing one (bcp_pq_stripes_async, window 0) on
+the same buffers, launches alternating as above, on two shapes:
+
+  equal16m  8 x 16 MiB stripes (--win-stripes of them, default 200): every
+            source is longer than the window and as long as the output, so
+            nothing is replayed and both kernels read and write the same
+            bytes -- the cost of the windowed form's per-source remap alone;
+            their outputs are compared with each other and with the host's
+  replay    one 24 MiB source and seven of 64 KiB: the windowed kernel replays
+            the short ones' first window (64 KiB and its padding) into every
+            later window, for the other they are zero padding, so the two do
+            different work -- described, not compared.  Bytes are the streams'
+            ((n + 2) x out_len, padding included) for the windowed kernel and
+            the bytes actually read and written for the other.
+
 One JSON line per figure, on stdout and appended to --out
-(default profiles/pq/pq_rate.jsonl).
+(default profiles/pq/pq_rate.jsonl; --windowed: profiles/pq/pq_win_rate.jsonl).
 
     python tools/pq_rate.py [--steps 20] [--warmup 3] [--stripes 12500] [--sweep]
+    python tools/pq_rate.py --windowed [--win-stripes 200]
 """
 import argparse
 import json
@@ -176,6 +193,106 @@ def device_shape(a, eng, q, name, lens_all, configs):
     return ok
 
 
+def replayed_rows(q, sources, first, nsrc, m, w):
+    """[nsrc][m] uint8: the replayed stream of every source of one stripe (w = 0: zero padding)."""
+    rows = np.zeros((nsrc, m), np.uint8)
+    for k in range(nsrc):
+        ptr, ln = sources[first + k]
+        if not ln:
+            continue
+        lw = (ln - 1) // w if w else 0
+        pad = np.zeros((lw + 1) * w if w else max(ln, m), np.uint8)
+        q.d2h(pad[:ln], ptr, ln)
+        q.sync()
+        j = np.arange(m, dtype=np.int64)
+        rows[k] = pad[np.where(j < (lw + 1) * w, j, lw * w + j % w)] if w else pad[:m]
+    return rows
+
+
+def windowed_shape(a, eng, q, name, lens, nstripes, same_output):
+    """The windowed GEN kernel (window W) against the existing one (window 0) on the same buffers."""
+    W = bcp.WINDOW_BYTES
+    align = lambda x: (x + 255) & ~255  # noqa: E731
+    m = max(lens)
+    src_bytes, out_bytes = nstripes * sum(align(x) for x in lens), nstripes * align(m)
+    src, out, qout = eng.alloc(src_bytes), eng.alloc(out_bytes), eng.alloc(out_bytes)
+    q.fill_synthetic(src, src_bytes, seed=1)
+    stripes = {0: [], W: []}
+    sources, qd, so_off = [], [], 0
+    for s in range(nstripes):
+        first = len(sources)
+        for x in lens:
+            sources.append((src + so_off, x))
+            so_off += align(x)
+        for w in stripes:
+            stripes[w].append((out + s * align(m), m, first, len(lens), w))
+        qd.append(qout + s * align(m))
+    so = (bcp.Source * len(sources))(*[bcp.Source(*x) for x in sources])
+    st = {w: (bcp.Stripe * nstripes)(*[bcp.Stripe(*x) for x in v]) for w, v in stripes.items()}
+    qdst = (bcp.ctypes.c_uint64 * nstripes)(*qd)
+    L = bcp.lib()
+
+    def plain():
+        bcp.check("bcp_pq_stripes_async", L.bcp_pq_stripes_async(q.h, st[0], nstripes, so, len(sources), qdst))
+
+    def win():
+        bcp.check("bcp_pq_stripes_win_async",
+                  L.bcp_pq_stripes_win_async(q.h, st[W], nstripes, so, len(sources), qdst))
+
+    def outputs(fn, sample):
+        q.memset(out, 0xA5, out_bytes)
+        q.memset(qout, 0xA5, out_bytes)
+        fn()
+        got = []
+        for s in sample:
+            gp, gq = np.empty(m, np.uint8), np.empty(m, np.uint8)
+            q.d2h(gp, stripes[0][s][0], m)
+            q.d2h(gq, qd[s], m)
+            got.append((gp, gq))
+        q.sync()
+        return got
+
+    sample = sorted({0, nstripes // 2, nstripes - 1})
+    got_w, got_p = outputs(win, sample), outputs(plain, sample)
+    good = True
+    for i, s in enumerate(sample[:2]):
+        for w, got in ((W, got_w), (0, got_p)):
+            hp, hq = host_pq(replayed_rows(q, sources, stripes[0][s][2], len(lens), m, w))
+            good &= np.array_equal(got[i][0], hp) and np.array_equal(got[i][1], hq)
+    if same_output:
+        good &= all(np.array_equal(x[0], y[0]) and np.array_equal(x[1], y[1]) for x, y in zip(got_w, got_p))
+    for _ in range(a.warmup):
+        win()
+        plain()
+    q.sync()
+    forms = {}
+    for key, fn in (("plain", plain), ("windowed", win)):
+        fn()
+        q.sync()
+        forms[key] = dict(desc_form=eng.option("last_desc_form"), desc_vecs=eng.option("last_desc_vecs"),
+                          blocks_per_cu=eng.option("pq_blocks_per_cu"))
+    q.mark(0)
+    for i in range(a.steps):
+        win()
+        q.mark(2 * i + 1)
+        plain()
+        q.mark(2 * i + 2)
+    q.sync()
+    win_ms = [q.elapsed_ms(2 * i, 2 * i + 1) for i in range(a.steps)]
+    plain_ms = [q.elapsed_ms(2 * i + 1, 2 * i + 2) for i in range(a.steps)]
+    win_bytes = nstripes * (len(lens) + 2) * m
+    plain_bytes = nstripes * (sum(lens) + 2 * m)
+    fw, fp = figures(win_ms, win_bytes), figures(plain_ms, plain_bytes)
+    emit(a.out, shape=name, lens=lens, window=W, stripes=nstripes, steps=a.steps, warmup=a.warmup,
+         windowed_bytes_per_launch=win_bytes, plain_bytes_per_launch=plain_bytes, windowed=fw, plain=fp, forms=forms,
+         windowed_ms_over_plain_ms=round(fw["ms_median"] / fp["ms_median"], 4),
+         same_work=same_output, sample_verified=bool(good),
+         windowed_ms=[round(x, 4) for x in win_ms], plain_ms=[round(x, 4) for x in plain_ms])
+    for p in (src, out, qout):
+        eng.free(p)
+    return bool(good)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--steps", type=int, default=20)
@@ -183,9 +300,23 @@ def main():
     ap.add_argument("--stripes", type=int, default=0, help="stripes of the uniform batch (default: bench.py's)")
     ap.add_argument("--shapes", default="uniform,mixed")
     ap.add_argument("--sweep", action="store_true")
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "pq", "pq_rate.jsonl"))
+    ap.add_argument("--windowed", action="store_true", help="the windowed GEN kernel against the existing one")
+    ap.add_argument("--win-stripes", type=int, default=200)
+    ap.add_argument("--out", default=None)
     a = ap.parse_args()
     assert 1 <= a.steps <= 31, "two marks per step, 64 timer slots"
+    if a.out is None:
+        a.out = os.path.join(ROOT, "profiles", "pq", "pq_win_rate.jsonl" if a.windowed else "pq_rate.jsonl")
+    if a.windowed:
+        eng = bcp.Engine(0)
+        q = eng.queue()
+        cus, name = eng.info()
+        emit(a.out, device=name, cus=cus, tool="pq_rate --windowed")
+        ok = windowed_shape(a, eng, q, "equal16m", [16 * MiB] * 8, a.win_stripes, True)
+        ok &= windowed_shape(a, eng, q, "replay", [24 * MiB] + [64 * KiB] * 7, a.win_stripes, False)
+        q.close()
+        eng.close()
+        sys.exit(0 if ok else 3)
     import bench
     S = a.stripes or bench.default_stripes(1, 0)
     eng = bcp.Engine(0)
