@@ -58,6 +58,20 @@ PQ_CHECK_CLEAN = (2 ** 64 - 1, 0, 0, 0)  # a stripe whose P and Q bodies hold
 CULPRIT_NONE, CULPRIT_DATA, CULPRIT_P, CULPRIT_Q, CULPRIT_MANY = range(5)
 
 
+class PqRepairResult(ctypes.Structure):
+    """bcp_pq_repair_result: PqCheckResult's fields (the state as found), then the bytes corrected and left."""
+    _fields_ = PqCheckResult._fields_ + [("fixed", ctypes.c_uint64), ("left", ctypes.c_uint64)]
+
+
+PQ_REPAIR_CLEAN = PQ_CHECK_CLEAN + (0, 0)
+REPAIR_PARITY, REPAIR_ALL = 1, 2  # the policy's mode: only P and Q files are written / chunks too
+VERDICT_CLEAN, VERDICT_REPAIR, VERDICT_UNLOCATED, VERDICT_POLICY = range(4)  # bcp_pq_repair_verdict
+
+
+class Timespec(ctypes.Structure):
+    _fields_ = [("tv_sec", ctypes.c_long), ("tv_nsec", ctypes.c_long)]
+
+
 class Rebuild2Stats(ctypes.Structure):
     _fields_ = [("xor_items", ctypes.c_uint64), ("q_items", ctypes.c_uint64), ("pq_items", ctypes.c_uint64),
                 ("unrecoverable", ctypes.c_uint64)]
@@ -116,6 +130,23 @@ class VerifyQStats(ctypes.Structure):
 
 
 QSTATE_CHECKED, QSTATE_NONE, QSTATE_BAD = range(3)
+
+
+class RepairQItem(ctypes.Structure):
+    """bcp_repair_q_item: VerifyQItem's fields for the store as found, then the repair's verdict."""
+    _fields_ = VerifyQItem._fields_ + [("repair", ctypes.c_uint32), ("reserved", ctypes.c_uint32),
+                                       ("bytes_fixed", ctypes.c_uint64)]
+
+
+class RepairQStats(ctypes.Structure):
+    _fields_ = [("q", VerifyQStats), ("none", ctypes.c_uint64), ("done", ctypes.c_uint64), ("dry", ctypes.c_uint64),
+                ("policy", ctypes.c_uint64), ("unlocated", ctypes.c_uint64), ("changed", ctypes.c_uint64),
+                ("failed", ctypes.c_uint64), ("files_written", ctypes.c_uint64), ("bytes_written", ctypes.c_uint64),
+                ("repair_launches", ctypes.c_uint64)]
+
+
+(REPAIRED_NONE, REPAIRED_DONE, REPAIRED_DRY, REPAIRED_POLICY, REPAIRED_UNLOCATED, REPAIRED_CHANGED,
+ REPAIRED_FAILED) = range(7)
 
 
 class PipelineOpts(ctypes.Structure):
@@ -196,6 +227,13 @@ _SIGS = {
     "bcp_pq_check_stripes_win_async": ([_V, ctypes.POINTER(Stripe), ctypes.c_uint32, ctypes.POINTER(Source),
                                         ctypes.c_uint32, ctypes.POINTER(ctypes.c_uint64), _V], ctypes.c_int),
     "bcp_pq_culprit": ([ctypes.POINTER(PqCheckResult), ctypes.POINTER(ctypes.c_int)], ctypes.c_int),
+    "bcp_pq_repair_stripes_async": ([_V, ctypes.POINTER(Stripe), ctypes.c_uint32, ctypes.POINTER(Source),
+                                     ctypes.c_uint32, ctypes.POINTER(ctypes.c_uint64),
+                                     ctypes.POINTER(ctypes.c_uint64), _V], ctypes.c_int),
+    "bcp_pq_repair_verdict": ([ctypes.POINTER(PqCheckResult), ctypes.c_uint32, ctypes.c_int, ctypes.c_uint32,
+                               ctypes.POINTER(ctypes.c_uint64)], ctypes.c_int),
+    "bcp_patch_file": ([ctypes.c_char_p, ctypes.c_uint64, _V, _V, ctypes.c_uint64, ctypes.c_uint64,
+                        ctypes.POINTER(Timespec), ctypes.POINTER(ctypes.c_uint64)], ctypes.c_int),
     "bcp_q_target": ([ctypes.c_uint64, ctypes.c_int], ctypes.c_int),
     "bcp_xor_parity": ([_V, ctypes.c_size_t, _V, ctypes.c_int], ctypes.c_int),
     "bcp_ring_create": ([_V, ctypes.c_int, ctypes.c_int, ctypes.POINTER(_V)], ctypes.c_int),
@@ -263,6 +301,10 @@ _SIGS = {
     "bcp_pipeline_verify": ([_V, ctypes.c_char_p, ctypes.c_int, ctypes.POINTER(WorkItem), ctypes.c_size_t,
                              ctypes.POINTER(VerifyItem), ctypes.c_char_p, _V, ctypes.POINTER(VerifyStats)],
                             ctypes.c_int),
+    "bcp_pipeline_repair_q": ([_V, ctypes.c_char_p, ctypes.c_int, ctypes.POINTER(WorkItem), ctypes.c_size_t,
+                               ctypes.c_int, ctypes.c_uint32, ctypes.c_int, ctypes.POINTER(RepairQItem),
+                               ctypes.c_char_p, ctypes.c_char_p, ctypes.c_char_p, _V,
+                               ctypes.POINTER(RepairQStats)], ctypes.c_int),
     "bcp_pipeline_verify_q": ([_V, ctypes.c_char_p, ctypes.c_int, ctypes.POINTER(WorkItem), ctypes.c_size_t,
                                ctypes.POINTER(VerifyQItem), ctypes.c_char_p, ctypes.c_char_p, _V,
                                ctypes.POINTER(VerifyQStats)], ctypes.c_int),
@@ -366,6 +408,33 @@ def pq_culprit(result) -> tuple:
     if kind < 0:
         raise BcpError("bcp_pq_culprit", kind)
     return kind, pos.value
+
+
+def pq_repair_verdict(result, nsrc: int, mode: int, max_members: int = 1) -> tuple:
+    """bcp_pq_repair_verdict: (VERDICT_*, allow) -- the members of a record a repair may write under the
+    policy (allow is 0 unless the verdict is VERDICT_REPAIR).  result: a PqCheckResult, the tuple of its
+    fields, or None (the null record: BcpError -EINVAL)."""
+    r = result if isinstance(result, PqCheckResult) or result is None else PqCheckResult(*result)
+    allow = ctypes.c_uint64(0)
+    v = lib().bcp_pq_repair_verdict(ctypes.byref(r) if r is not None else None, nsrc, mode, max_members,
+                                    ctypes.byref(allow))
+    if v < 0:
+        raise BcpError("bcp_pq_repair_verdict", v)
+    return v, allow.value
+
+
+def patch_file(path: str, body_off: int, was, now, expect_size: int, expect_mtime_ns: int) -> int:
+    """bcp_patch_file: write the 4 KiB blocks in which `now` differs from `was` (equally long host
+    buffers, images of the file from body_off on) into the existing file and put its times back;
+    returns the bytes written.  BcpError -ESTALE when the file's size or mtime (ns) is not the expected."""
+    (a, n), (b, m) = _host_addr(was, None), _host_addr(now, None)
+    if n != m:
+        raise ValueError("patch_file: was and now differ in length")
+    ts = Timespec(expect_mtime_ns // 10 ** 9, expect_mtime_ns % 10 ** 9)
+    written = ctypes.c_uint64(0)
+    call("bcp_patch_file", path.encode(), body_off, _V(a), _V(b), n, expect_size, ctypes.byref(ts),
+         ctypes.byref(written))
+    return written.value
 
 
 def device_count() -> int:
@@ -539,6 +608,16 @@ class Queue:
         qb = (ctypes.c_uint64 * max(len(q_body), 1))(*q_body)
         call("bcp_pq_check_stripes_win_async" if windowed else "bcp_pq_check_stripes_async", self.h, st,
              len(stripes), so, len(sources), qb, _V(results_ptr))
+
+    def pq_repair(self, stripes, sources, q_body, allow, results_ptr: int):
+        """pq_check that also corrects in place the bad bytes whose member allow[s] admits (bit layout of
+        PqCheckResult.members; None: the null pointer); the sources and bodies are written, so stripes
+        must not share them.  results_ptr: device memory for len(stripes) PqRepairResult records."""
+        st = (Stripe * max(len(stripes), 1))(*[Stripe(*s) for s in stripes])
+        so = (Source * max(len(sources), 1))(*[Source(*s) for s in sources])
+        qb = (ctypes.c_uint64 * max(len(q_body), 1))(*q_body)
+        al = None if allow is None else (ctypes.c_uint64 * max(len(allow), 1))(*allow)
+        call("bcp_pq_repair_stripes_async", self.h, st, len(stripes), so, len(sources), qb, al, _V(results_ptr))
 
     def fill_synthetic(self, dptr: int, nbytes: int, seed: int, byte_offset: int = 0):
         call("bcp_dev_fill_synthetic_async", self.h, _V(dptr), nbytes, seed, byte_offset)
@@ -909,6 +988,19 @@ class Pipeline:
         call("bcp_pipeline_verify_q", self.h, store_root.encode(), ntargets, arr, len(items), res,
              bad_list.encode() if bad_list else None, culprit_list.encode() if culprit_list else None, log,
              ctypes.byref(st))
+        del keep
+        return st, list(res[:len(items)])
+
+    def repair_q(self, store_root: str, ntargets: int, items, mode: int, max_members: int = 1, dry_run: bool = False,
+                 bad_list: str | None = None, culprit_list: str | None = None, repaired_list: str | None = None,
+                 log=None):
+        """bcp_pipeline_repair_q (the scrub with Q that corrects what it blames): (RepairQStats, [RepairQItem])."""
+        arr, keep = _items(items)
+        st = RepairQStats()
+        res = (RepairQItem * max(len(items), 1))()
+        enc = lambda p: p.encode() if p else None  # noqa: E731
+        call("bcp_pipeline_repair_q", self.h, store_root.encode(), ntargets, arr, len(items), mode, max_members,
+             int(bool(dry_run)), res, enc(bad_list), enc(culprit_list), enc(repaired_list), log, ctypes.byref(st))
         del keep
         return st, list(res[:len(items)])
 

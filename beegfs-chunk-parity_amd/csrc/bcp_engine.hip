@@ -42,7 +42,7 @@ struct bcp_engine {
   pthread_mutex_t lock = PTHREAD_MUTEX_INITIALIZER;
   std::atomic<int> last_stream_vecs{0};  // U of the latest xor_stream launch (tools)
   std::atomic<int> last_desc_vecs{0};    // U of the latest descriptor-kernel launch (tools)
-  std::atomic<int> last_desc_form{0};    // 1 xor_desc (desc_tiles), 2 xor_desc_args, 3 check_desc, 4 / 5 / 6 pq_desc gen / solve / check, 7 / 8 / 9 their windowed forms
+  std::atomic<int> last_desc_form{0};    // 1 xor_desc (desc_tiles), 2 xor_desc_args, 3 check_desc, 4 / 5 / 6 pq_desc gen / solve / check, 7 / 8 / 9 their windowed forms, 10 pq_repair_desc
 };
 
 namespace {
@@ -1224,7 +1224,9 @@ const Gf256 g_gf;
 
 // All forms: `lost` is SOLVE; else q_dst gives the Q bodies, written (GEN) or
 // with `check` (nstripes device records, initialised on the queue first)
-// read beside the P bodies at dst (CHECK).
+// read beside the P bodies at dst (CHECK).  `repair` with `allow` is the
+// REPAIR form: CHECK's batch and validation, its own records, the stripes'
+// masks in their table records, never windowed.
 // The staged tables are the stripes' records, their source runs copied in the
 // caller's order, and one record per tile; they go through stage_tables with
 // the pointer-table threshold, since the kernel reads them once per tile.
@@ -1234,7 +1236,8 @@ const Gf256 g_gf;
 // plain launch.
 static int submit_pq(bcp_queue *q, const bcp_stripe *stripes, uint32_t nstripes, const bcp_source *sources,
                      uint32_t nsources, const uint64_t *q_dst, const bcp_pq_lost *lost,
-                     bcp_pq_check_result *check = nullptr, bool win = false) {
+                     bcp_pq_check_result *check = nullptr, bool win = false, const uint64_t *allow = nullptr,
+                     bcp_pq_repair_result *repair = nullptr) {
   bcp_engine *e = q->eng;
   uint64_t tiles8 = 0, nstaged = 0;
   bool windowed = false;
@@ -1259,7 +1262,7 @@ static int submit_pq(bcp_queue *q, const bcp_stripe *stripes, uint32_t nstripes,
       if (l.len_x > s.out_len || (two && l.len_y > s.out_len)) return -EINVAL;
       if ((l.len_x && !l.dst_x) || (two && l.len_y && !l.dst_y)) return -EINVAL;
       cover = std::max(l.len_x, two ? l.len_y : (uint64_t)0);
-    } else if (s.out_len && (!q_dst[i] || (check && !s.dst))) {
+    } else if (s.out_len && (!q_dst[i] || ((check || repair) && !s.dst))) {
       return -EINVAL;
     }
     tiles8 += (cover + desc_tile_bytes(8) - 1) / desc_tile_bytes(8);
@@ -1270,6 +1273,11 @@ static int submit_pq(bcp_queue *q, const bcp_stripe *stripes, uint32_t nstripes,
     if (q->broken) return -EIO;
     (void)hipGetLastError();
     HIP_RC(launch_pq_check_init(q->stream, check, nstripes));
+  }
+  if (repair) {
+    if (q->broken) return -EIO;
+    (void)hipGetLastError();
+    HIP_RC(launch_pq_repair_init(q->stream, repair, nstripes));
   }
   if (tiles8 == 0) return 0;
   int vecs = e->tuning.desc_vecs;
@@ -1342,6 +1350,7 @@ static int submit_pq(bcp_queue *q, const bcp_stripe *stripes, uint32_t nstripes,
       } else {
         r.p = s.dst;
         r.q = q_dst[i];
+        if (allow) r.allow = allow[i];
       }
       hs[i] = r;
       if (s.nsrc) memcpy(hso + r.first_src, sources + s.first_src, (size_t)s.nsrc * sizeof(bcp_source));
@@ -1378,12 +1387,13 @@ static int submit_pq(bcp_queue *q, const bcp_stripe *stripes, uint32_t nstripes,
   if (q->broken) return -EIO;
   (void)hipGetLastError();  // see launch_stream
   const int form = check ? 2 : lost ? 1 : 0;
-  const hipError_t le = windowed ? launch_pq_win(q->stream, grid, vecs, form, bw, check)
-                        : check  ? launch_pq_check(q->stream, grid, vecs, b, check)
-                                 : launch_pq(q->stream, grid, vecs, lost != nullptr, b);
+  const hipError_t le = repair     ? launch_pq_repair(q->stream, grid, vecs, b, repair)
+                        : windowed ? launch_pq_win(q->stream, grid, vecs, form, bw, check)
+                        : check    ? launch_pq_check(q->stream, grid, vecs, b, check)
+                                   : launch_pq(q->stream, grid, vecs, lost != nullptr, b);
   if (le == hipSuccess) {
     e->last_desc_vecs.store(vecs, std::memory_order_relaxed);
-    e->last_desc_form.store((windowed ? 7 : 4) + form, std::memory_order_relaxed);
+    e->last_desc_form.store(repair ? 10 : (windowed ? 7 : 4) + form, std::memory_order_relaxed);
   }
   if ((rc = queue_launched(q, le, (uint64_t)ntiles + (uint64_t)grid))) return rc;
   HIP_RC(hipEventRecord(slot->done, q->stream));
@@ -1419,7 +1429,17 @@ extern "C" int bcp_pq_check_stripes_async(bcp_queue *q, const bcp_stripe *stripe
   return submit_pq(q, stripes, nstripes, sources, nsources, q_body, nullptr, results_dev);
 }
 
-// The same three over window replay (bcp.h): a stripe's window may be 0 or a
+extern "C" int bcp_pq_repair_stripes_async(bcp_queue *q, const bcp_stripe *stripes, uint32_t nstripes,
+                                           const bcp_source *sources, uint32_t nsources, const uint64_t *q_body,
+                                           const uint64_t *allow, bcp_pq_repair_result *results_dev) {
+  if (!q || !stripes || !q_body || !allow || !results_dev || (nsources && !sources)) return -EINVAL;
+  if (!nstripes) return 0;
+  int rc = set_device(q->eng);
+  if (rc) return rc;
+  return submit_pq(q, stripes, nstripes, sources, nsources, q_body, nullptr, nullptr, false, allow, results_dev);
+}
+
+// The first three over window replay (bcp.h): a stripe's window may be 0 or a
 // multiple of the largest tile.
 extern "C" int bcp_pq_stripes_win_async(bcp_queue *q, const bcp_stripe *stripes, uint32_t nstripes,
                                         const bcp_source *sources, uint32_t nsources, const uint64_t *q_dst) {

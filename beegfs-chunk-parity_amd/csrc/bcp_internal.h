@@ -278,19 +278,20 @@ struct RingArgs {
 
 // ---------------------------------------------------------------------------
 // P + Q parity (bcp_pq.hip; bcp_pq_stripes_async, bcp_pq_recover_stripes_async,
-// bcp_pq_check_stripes_async, and their _win namesakes further down).
+// bcp_pq_check_stripes_async, bcp_pq_repair_stripes_async, and the first
+// three's _win namesakes further down).
 // One record per stripe and one per tile, both written by the host: the
 // sources of a run stay in the caller's position order (source k has
 // coefficient g^k), so nothing here is sorted.
 // ---------------------------------------------------------------------------
 struct alignas(16) PqStripe {
-    uint64_t p, q;          // GEN: P / Q output (p 0: no P); SOLVE: P / Q body (p 0: P is lost); CHECK: P / Q body
-    uint64_t out_len;       // GEN: bytes of each output; SOLVE, CHECK: readable bytes of p and q
+    uint64_t p, q;          // GEN: P / Q output (p 0: no P); SOLVE: P / Q body (p 0: P is lost); CHECK, REPAIR: P / Q body
+    uint64_t out_len;       // GEN: bytes of each output; SOLVE, CHECK, REPAIR: readable bytes of p and q
     uint32_t first_src, nsrc;
     uint64_t dx, len_x;     // SOLVE: member x, its first len_x bytes
     uint64_t dy, len_y;     // SOLVE: member y (len_y 0: not asked for)
     uint32_t ca, cb;        // SOLVE: D_x = ca * Ps ^ cb * Qs over GF(2^8)
-    uint32_t pad[2];
+    uint64_t allow;         // REPAIR: the members that may be written, bit layout of bcp_pq_check_result.members
 };
 static_assert(sizeof(PqStripe) == 80, "five 16-byte scalar loads");
 struct PqTile {
@@ -313,6 +314,11 @@ hipError_t launch_pq(hipStream_t st, int grid, int vecs, bool solve, const PqBat
 // n records to {UINT64_MAX, 0, 0, 0}.
 hipError_t launch_pq_check_init(hipStream_t st, bcp_pq_check_result *res, uint32_t n);
 hipError_t launch_pq_check(hipStream_t st, int grid, int vecs, const PqBatch &b, bcp_pq_check_result *res);
+// REPAIR form (bcp_pq_repair_stripes_async): CHECK's batch with PqStripe.allow
+// set; the bodies and sources are written where a bad byte's member is allowed.
+// launch_pq_repair_init sets n records to {UINT64_MAX, 0, 0, 0, 0, 0}.
+hipError_t launch_pq_repair_init(hipStream_t st, bcp_pq_repair_result *res, uint32_t n);
+hipError_t launch_pq_repair(hipStream_t st, int grid, int vecs, const PqBatch &b, bcp_pq_repair_result *res);
 
 // The windowed forms (bcp_pq_*_win_async): a batch in which some stripe has a
 // window W (a multiple of kPqWindowUnit, so a tile lies in one window and the

@@ -41,6 +41,11 @@
  * (bcp_pipeline_verify_q) an item whose Q file is in order gets one more
  * source row, the Q body, and its stripe goes in a launch of its own per batch
  * (bcp_pq_check_stripes_async): 32 bytes come back, the syndromes' verdict.
+ * A repair run (bcp_pipeline_repair_q) is that run with one more stage in the
+ * batch's completion, before the slot is released: the MISMATCH items the
+ * policy admits go through bcp_pq_repair_stripes_async and a second check on
+ * the slot's device slab, on a queue of the completion thread's own, and the
+ * blocks that changed are patched into the files (repair_batch).
  *
  * Q parity (bcp_pipeline_set_q_parity, bcp_pipeline_rebuild2; bcp_task.h): a
  * task may have a second output, placed after the first in the output slab
@@ -266,6 +271,8 @@ typedef struct {
     int vq;
     uint32_t q_state;
     uint64_t q_bad, members;             /* vq, CHECKED: the rest of the record (p_bad is bad_bytes) */
+    struct timespec mtime[MAX_STORAGE_TARGETS]; /* verify: mtime of source k's file at stat time (repair) */
+    uint64_t allow;                      /* repair: the members that may be written */
     /* Q parity.  gen: q_st is the item's Q target when the run writes its Q
      * file (-1: none).  rebuild2: pq = 1 recovers the victim from Q alone (P is
      * lost too), pq = 2 both victims (p, p2) from P and Q; the sources are then
@@ -367,6 +374,17 @@ static uint64_t read_extent(const task *t, int k, int direct)
     return direct ? RUP_PAGE(t->src_off[k] + t->size[k]) : t->size[k];
 }
 
+/* A repair run's policy, results and counts (bcp_pipeline_repair_q); only the
+ * completion thread touches them while the run is on. */
+typedef struct repair_ctx {
+    int mode, dry_run;
+    uint32_t max_members;
+    bcp_repair_q_item *res; /* per work item: repair, bytes_fixed */
+    int list_fd;            /* the repaired list (or -1) */
+    uint64_t files_written, bytes_written, launches;
+    int errors;
+} repair_ctx;
+
 typedef struct {
     job j;
     const char *root;
@@ -390,6 +408,10 @@ typedef struct {
     FILE *log;
     int *errors;
     int *dev_rc;
+    struct repair_ctx *rp; /* a repair run (or NULL), and what its stage needs of the batch's lane */
+    bcp_engine *eng;
+    bcp_queue *qr;
+    int dir;
 } complete_arg;
 
 static pthread_mutex_t g_stat_lock = PTHREAD_MUTEX_INITIALIZER;
@@ -432,8 +454,10 @@ static void do_stat(job *p)
         chunk_file(fn, sizeof(fn), a->root, t->holders[n], "parity", t->path);
         int fd = open(fn, O_RDONLY);
         if (fd >= 0) {
-            if (fstat(fd, &st) == 0)
+            if (fstat(fd, &st) == 0) {
                 fsize = (uint64_t)st.st_size;
+                t->mtime[n] = st.st_mtim;
+            }
             have = fsize >= (uint64_t)n * 8u && pread(fd, header, (size_t)n * 8u, 0) == (ssize_t)((size_t)n * 8u);
             close(fd);
         }
@@ -446,6 +470,7 @@ static void do_stat(job *p)
             if (stat(fn, &st) == 0) {
                 cur = (uint64_t)st.st_size;
                 stale |= st.st_mtime > t->timestamp;
+                t->mtime[k] = st.st_mtim;
             }
             resized |= cur != header[k];
             t->size[k] = header[k];
@@ -468,8 +493,10 @@ static void do_stat(job *p)
                 chunk_file(fn, sizeof(fn), a->root, t->q_st, "parityq", t->path);
                 fd = open(fn, O_RDONLY);
                 if (fd >= 0) {
-                    if (fstat(fd, &st) == 0)
+                    if (fstat(fd, &st) == 0) {
                         qsize = (uint64_t)st.st_size;
+                        t->mtime[t->n] = st.st_mtim;
+                    }
                     qhave = qsize >= (uint64_t)n * 8u && pread(fd, hq, (size_t)n * 8u, 0) == (ssize_t)((size_t)n * 8u);
                     close(fd);
                 }
@@ -772,6 +799,177 @@ static void do_write(job *p)
 
 /* Completion stage (one thread, batches in order): wait for the batch's D2H,
  * then hand its parity files to the io pool (behind every queued read). */
+/* ---- scrub repair: the stage between a batch's records and its slot's release */
+static uint64_t data_off(const task *t, int k, int page_layout);
+
+#define REPAIR_PENDING 0xFFu /* admitted by the policy: in the repair launch */
+
+/* Size a verify task's source file had at stat time: a chunk is its header
+ * entry, a parity file the header and the body. */
+static uint64_t repair_fsize(const task *t, int k)
+{
+    return t->src_off[k] + t->size[k];
+}
+
+static void push_repaired(int fd, const char *path, int kind, int target, uint64_t bytes)
+{
+    static const char *const name[3] = {"data", "p", "q"};
+    if (fd < 0)
+        return;
+    const size_t cap = strlen(path) + 64;
+    char *line = malloc(cap);
+    if (!line)
+        return;
+    const int len = snprintf(line, cap, "%s\t%s\t%d\t%llu\n", path, name[kind], target, (unsigned long long)bytes);
+    ssize_t w = write(fd, line, (size_t)len);
+    (void)w;
+    free(line);
+}
+
+/* Write back the allowed members of one repaired, re-checked item: the slab
+ * still holds each file as read (was), the device the corrected bytes (now).
+ * Returns the item's BCP_REPAIRED_* verdict. */
+static uint32_t repair_write_back(const complete_arg *a, const task *t)
+{
+    repair_ctx *R = a->rp;
+    int src[MAX_STORAGE_TARGETS], ns = 0;
+    char fn[4352];
+    for (int k = 0; k < t->parity_src; k++)
+        if (t->allow >> k & 1)
+            src[ns++] = k;
+    if (t->allow & BCP_PQ_BAD_P)
+        src[ns++] = t->parity_src;
+    if (t->allow & BCP_PQ_BAD_Q)
+        src[ns++] = t->q_src;
+    /* a file that changed under the scrub leaves the whole item alone */
+    for (int i = 0; i < ns; i++) {
+        const int k = src[i];
+        struct stat st;
+        chunk_file(fn, sizeof(fn), a->root, t->holders[k], k_dir[src_kind(t, k)], t->path);
+        if (stat(fn, &st) != 0)
+            return errno == ENOENT ? BCP_REPAIRED_CHANGED : BCP_REPAIRED_FAILED;
+        if ((uint64_t)st.st_size != repair_fsize(t, k) || st.st_mtim.tv_sec != t->mtime[k].tv_sec ||
+            st.st_mtim.tv_nsec != t->mtime[k].tv_nsec)
+            return BCP_REPAIRED_CHANGED;
+    }
+    for (int i = 0; i < ns; i++) {
+        const int k = src[i], kind = src_kind(t, k);
+        const uint64_t off = data_off(t, k, a->dir), len = t->size[k];
+        uint8_t *was = malloc(len ? len : 1);
+        if (!was)
+            return BCP_REPAIRED_FAILED;
+        memcpy(was, a->S->h_in + off, len);
+        int rc = bcp_d2h_async(a->qr, a->S->h_in + off, (const uint8_t *)a->S->d_in + off, (size_t)len);
+        if (!rc)
+            rc = bcp_queue_sync(a->qr);
+        uint64_t bw = 0;
+        chunk_file(fn, sizeof(fn), a->root, t->holders[k], k_dir[kind], t->path);
+        if (!rc)
+            rc = bcp_patch_file(fn, t->src_off[k], was, a->S->h_in + off, len, repair_fsize(t, k), &t->mtime[k], &bw);
+        free(was);
+        if (bw) {
+            R->files_written++;
+            R->bytes_written += bw;
+            push_repaired(R->list_fd, t->path, kind, t->holders[k], bw);
+        }
+        if (rc == -ESTALE)
+            return BCP_REPAIRED_CHANGED;
+        if (rc) {
+            if (a->log)
+                fprintf(a->log, "bcp_pipeline: repair of '%s' failed: %s\n", fn, bcp_strerror(rc));
+            return BCP_REPAIRED_FAILED;
+        }
+    }
+    return BCP_REPAIRED_DONE;
+}
+
+/* The batch's MISMATCH items after their records are in: the policy on the
+ * host, then one repair launch and one check launch over the admitted stripes
+ * where they lie in the slot's device slab, then the write-back. */
+static void repair_batch(const complete_arg *a)
+{
+    repair_ctx *R = a->rp;
+    size_t n = 0, nsrc = 0;
+    for (size_t i = a->first; i < a->last; i++) {
+        task *t = &a->tasks[i];
+        if (t->status != BCP_VERIFY_MISMATCH)
+            continue;
+        bcp_repair_q_item *v = &R->res[t->item];
+        v->repair = BCP_REPAIRED_UNLOCATED;
+        if (!t->vq || t->q_state != BCP_QSTATE_CHECKED || t->max_cs > WINDOW)
+            continue;
+        const bcp_pq_check_result r = {t->first_bad, t->bad_bytes, t->q_bad, t->members};
+        const int vd = bcp_pq_repair_verdict(&r, (uint32_t)t->parity_src, R->mode, R->max_members, &t->allow);
+        if (vd == BCP_VERDICT_POLICY)
+            v->repair = BCP_REPAIRED_POLICY;
+        if (vd != BCP_VERDICT_REPAIR)
+            continue;
+        v->repair = REPAIR_PENDING;
+        n++;
+        nsrc += (size_t)t->parity_src;
+    }
+    if (!n)
+        return;
+    const size_t rec = sizeof(bcp_pq_repair_result) + sizeof(bcp_pq_check_result);
+    bcp_stripe *st = malloc(n * sizeof(*st));
+    bcp_source *so = malloc((nsrc ? nsrc : 1) * sizeof(*so));
+    uint64_t *qb = malloc(2 * n * sizeof(*qb)), *al = qb ? qb + n : NULL;
+    uint8_t *h = malloc(n * rec);
+    void *d = NULL;
+    int rc = st && so && qb && h ? bcp_dev_alloc(a->eng, n * rec, &d) : -ENOMEM;
+    if (!rc) {
+        uint32_t j = 0, s = 0;
+        for (size_t i = a->first; i < a->last; i++) {
+            const task *t = &a->tasks[i];
+            if (t->status != BCP_VERIFY_MISMATCH || R->res[t->item].repair != REPAIR_PENDING)
+                continue;
+            const int nfold = t->parity_src;
+            st[j] = (bcp_stripe){(uint64_t)a->S->d_in + data_off(t, nfold, a->dir), t->out_len, s, (uint32_t)nfold, 0};
+            qb[j] = (uint64_t)a->S->d_in + data_off(t, t->q_src, a->dir);
+            al[j] = t->allow;
+            for (int k = 0; k < nfold; k++)
+                so[s++] = (bcp_source){(uint64_t)a->S->d_in + data_off(t, k, a->dir), t->size[k]};
+            j++;
+        }
+        bcp_pq_repair_result *d_rep = d;
+        bcp_pq_check_result *d_chk = (bcp_pq_check_result *)(d_rep + n);
+        if (!(rc = bcp_pq_repair_stripes_async(a->qr, st, (uint32_t)n, so, s, qb, al, d_rep)) &&
+            !(rc = bcp_pq_check_stripes_async(a->qr, st, (uint32_t)n, so, s, qb, d_chk)) &&
+            !(rc = bcp_d2h_async(a->qr, h, d, n * rec)))
+            rc = bcp_queue_sync(a->qr);
+        R->launches++;
+    }
+    const bcp_pq_repair_result *rep = (const bcp_pq_repair_result *)h;
+    const bcp_pq_check_result *chk = rep ? (const bcp_pq_check_result *)(rep + n) : NULL;
+    size_t j = 0;
+    for (size_t i = a->first; i < a->last; i++) {
+        const task *t = &a->tasks[i];
+        bcp_repair_q_item *v = &R->res[t->item];
+        if (t->status != BCP_VERIFY_MISMATCH || v->repair != REPAIR_PENDING)
+            continue;
+        if (rc)
+            v->repair = BCP_REPAIRED_FAILED;
+        else if (rep[j].left)
+            v->repair = BCP_REPAIRED_UNLOCATED;
+        else if (chk[j].members || rep[j].members != t->members) /* nothing reaches a disk unverified */
+            v->repair = BCP_REPAIRED_FAILED;
+        else
+            v->repair = R->dry_run ? BCP_REPAIRED_DRY : repair_write_back(a, t);
+        if (v->repair == BCP_REPAIRED_DONE || v->repair == BCP_REPAIRED_DRY)
+            v->bytes_fixed = rep[j].fixed;
+        R->errors += v->repair == BCP_REPAIRED_FAILED;
+        j++;
+    }
+    if (rc && a->log)
+        fprintf(a->log, "bcp_pipeline: repair launch failed: %s\n", bcp_strerror(rc));
+    if (d)
+        bcp_dev_free(a->eng, d);
+    free(st);
+    free(so);
+    free(qb);
+    free(h);
+}
+
 static void do_complete(job *p)
 {
     /* The run frees its job arrays once every write of the batch has counted
@@ -802,8 +1000,11 @@ static void do_complete(job *p)
                 t->bad_bytes = r->bad_bytes;
                 t->status = r->bad_bytes ? BCP_VERIFY_MISMATCH : BCP_VERIFY_OK;
             }
-            latch_down(done);
         }
+        if (!rc && a.rp)
+            repair_batch(&a); /* before the slot is released: it corrects in the slot's slabs */
+        for (size_t i = a.first; i < a.last; i++)
+            latch_down(done);
         return;
     }
     if (rc) {
@@ -863,6 +1064,7 @@ static void slot_free(bcp_engine *e, slot *s)
 typedef struct {
     bcp_engine *eng;
     bcp_queue *qh, *qk, *qd;
+    bcp_queue *qr;        /* a repair run's launches and copies (completion thread); created by the first such run */
     slot *slots;
 } dev_lane;
 
@@ -884,6 +1086,7 @@ struct bcp_pipeline {
     int q_on;           /* bcp_pipeline_set_q_parity */
     int q_win;          /* bcp_pipeline_set_q_windowed */
     uint64_t q_written, q_no_target, q_windowed; /* of the last run */
+    repair_ctx *repair; /* during a repair run (bcp_pipeline_repair_q) */
     uint8_t *r2_unrec;  /* during a rebuild2 run: per item, 1 = unrecoverable after the stat phase */
     bcp_pipeline_timing last; /* of the last run */
 };
@@ -929,7 +1132,9 @@ int bcp_pipeline_destroy(bcp_pipeline *pl)
                 bcp_queue_destroy(L->qk);
             if (L->qd)
                 bcp_queue_destroy(L->qd);
-            L->qh = L->qk = L->qd = NULL;
+            if (L->qr)
+                bcp_queue_destroy(L->qr);
+            L->qh = L->qk = L->qd = L->qr = NULL;
         }
         free_slots(pl);
         for (int d = 0; d < pl->ndev; d++)
@@ -1645,7 +1850,8 @@ static int pipeline_exec(bcp_pipeline *pl, const char *store_root, task *tasks, 
         latch_init(&S->writes, verify ? (long)(last - first) : nwrites);
         S->busy = 1;
         complete_arg *ca = &cargs[b];
-        *ca = (complete_arg){{0}, S, store_root, tasks, wa, first, last, &pl->io, log, &errors, &dev_rc};
+        *ca = (complete_arg){{0}, S, store_root, tasks, wa, first, last, &pl->io, log, &errors, &dev_rc,
+                             qres ? pl->repair : NULL, L->eng, L->qr, dir};
         pool_push(&pl->completer, &ca->j, do_complete);
         for (size_t i = first; i < last && !verify; i++)
             bytes_written += (tasks[i].rebuild ? 0 : 8u * (uint64_t)tasks[i].n) + tasks[i].out_len +
@@ -2024,6 +2230,82 @@ out:
     if (culprit_fd >= 0)
         close(culprit_fd);
     free(tasks);
+    if (res != results)
+        free(res);
+    return rc;
+}
+
+/* The scrub with repair: bcp_pipeline_verify_q's run with the repair stage in
+ * its completions (repair_batch), so the verdicts and both lists are that
+ * function's own. */
+int bcp_pipeline_repair_q(bcp_pipeline *pl, const char *store_root, int ntargets, const bcp_work_item *items,
+                          size_t nitems, int mode, uint32_t max_members, int dry_run, bcp_repair_q_item *results,
+                          const char *bad_list_path, const char *culprit_list_path, const char *repaired_list_path,
+                          FILE *log, bcp_repair_q_stats *stats)
+{
+    if (!pl || (mode != BCP_REPAIR_PARITY && mode != BCP_REPAIR_ALL) || max_members < 1)
+        return -EINVAL;
+    int rc = 0;
+    for (int d = 0; d < pl->ndev && !rc; d++)
+        if (!pl->dev[d].qr)
+            rc = bcp_queue_create(pl->dev[d].eng, &pl->dev[d].qr);
+    if (rc)
+        return rc;
+    bcp_repair_q_item *res = results ? results : calloc(nitems ? nitems : 1, sizeof(*res));
+    bcp_verify_q_item *vq = calloc(nitems ? nitems : 1, sizeof(*vq));
+    repair_ctx R = {mode, dry_run != 0, max_members, res, -1, 0, 0, 0, 0};
+    if (!res || !vq) {
+        rc = -ENOMEM;
+        goto out;
+    }
+    memset(res, 0, (nitems ? nitems : 1) * sizeof(*res));
+    if (repaired_list_path) {
+        R.list_fd = open(repaired_list_path, O_WRONLY | O_CREAT | O_TRUNC | O_APPEND, S_IRUSR | S_IWUSR);
+        if (R.list_fd < 0) {
+            rc = -errno;
+            goto out;
+        }
+    }
+    bcp_repair_q_stats rs;
+    memset(&rs, 0, sizeof(rs));
+    pl->repair = &R;
+    rc = bcp_pipeline_verify_q(pl, store_root, ntargets, items, nitems, vq, bad_list_path, culprit_list_path, log, &rs.q);
+    pl->repair = NULL;
+    if (rc == -EINVAL || rc == -ENOMEM) /* (refused before anything ran: no verdicts) */
+        goto out;
+    for (size_t i = 0; i < nitems; i++) {
+        bcp_repair_q_item *v = &res[i];
+        v->status = vq[i].status;
+        v->q_state = vq[i].q_state;
+        v->culprit = vq[i].culprit;
+        v->target = vq[i].target;
+        v->first_bad = vq[i].first_bad;
+        v->p_bad = vq[i].p_bad;
+        v->q_bad = vq[i].q_bad;
+        if (v->status != BCP_VERIFY_MISMATCH)
+            v->repair = BCP_REPAIRED_NONE;
+        else if (v->repair == BCP_REPAIRED_NONE || v->repair == REPAIR_PENDING) { /* its repair stage never ran */
+            v->repair = BCP_REPAIRED_FAILED;
+            R.errors++;
+        }
+        rs.none += v->repair == BCP_REPAIRED_NONE;
+        rs.done += v->repair == BCP_REPAIRED_DONE;
+        rs.dry += v->repair == BCP_REPAIRED_DRY;
+        rs.policy += v->repair == BCP_REPAIRED_POLICY;
+        rs.unlocated += v->repair == BCP_REPAIRED_UNLOCATED;
+        rs.changed += v->repair == BCP_REPAIRED_CHANGED;
+        rs.failed += v->repair == BCP_REPAIRED_FAILED;
+    }
+    rs.q.v.errors += R.errors;
+    rs.files_written = R.files_written;
+    rs.bytes_written = R.bytes_written;
+    rs.repair_launches = R.launches;
+    if (stats)
+        *stats = rs;
+out:
+    if (R.list_fd >= 0)
+        close(R.list_fd);
+    free(vq);
     if (res != results)
         free(res);
     return rc;

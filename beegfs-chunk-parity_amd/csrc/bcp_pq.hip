@@ -8,7 +8,7 @@
 // four packed bytes of a dword at a time (mul2): no multiply, no table, no
 // LDS.  One pass over the sources yields both.
 //
-// Three forms of that pass:
+// Four forms of that pass:
 //   GEN    the epilogue stores Q, and P when the stripe has a P address;
 //   SOLVE  the sources are the survivors (lost positions have len 0 and
 //          contribute 2*q steps only), the P and Q bodies are loaded with the
@@ -22,8 +22,13 @@
 //          locates every bad byte -- Ps only: P, Qs only: Q, both: the data
 //          position k with g^k * Ps = Qs -- and commits first offset, counts
 //          and member mask to the stripe's record (bcp_pq_check_result).
+//   REPAIR CHECK's prologue, pass and clean path; the mismatch path also
+//          corrects in place every bad byte whose member the stripe's mask
+//          allows -- P ^= Ps, Q ^= Qs, D_k ^= Ps -- and counts the bytes it
+//          fixed and the bytes it left (bcp_pq_repair_result).  No window
+//          form: a replayed byte is not tile-local.
 //
-// Each form also exists over window replay (pq_win_desc, the _win entry
+// The first three also exist over window replay (pq_win_desc, the _win entry
 // points): D_k is then the reference's replayed stream R_k of source k (bcp.h),
 // which the kernel reads by remapping, per source and tile, the offset it loads
 // from (pq_eff_off); outputs and bodies are addressed as before.
@@ -246,14 +251,118 @@ __device__ __forceinline__ void pq_check_commit(bcp_pq_check_result *rec, const 
   }
 }
 
-enum PqForm { kPqGen = 0, kPqSolve = 1, kPqCheck = 2 };
+// ---- REPAIR form: the same verdict, and the bytes put right ---------------
+// The bytes of dword `val` (Ps or Qs) flagged in m (bit 7 per byte) XORed into
+// the n (<= 4) writable bytes at `at`.  A byte of a member belongs to the one
+// lane of the one tile that loaded it, so a plain read-modify-write is safe at
+// any alignment.  Returns the bytes written.
+__device__ __forceinline__ uint32_t pq_fix_bytes(uint64_t at, uint32_t m, uint32_t val, uint32_t n) {
+  uint32_t done = 0;
+  while (m) {
+    const uint32_t b = (uint32_t)__builtin_ctz(m) >> 3;
+    m &= m - 1u;
+    if (b < n) {
+      glob<unsigned char> *o = gp<unsigned char>(at + b);
+      *o = (unsigned char)(*o ^ (unsigned char)(val >> (8u * b)));
+      done++;
+    }
+  }
+  return done;
+}
+
+// Sibling of pq_check_commit: the record's first four fields are the state as
+// found; `allow` (the stripe's mask, bit layout of members) decides which
+// members are written.  pbody, qbody: the bodies at stripe offset 0.  A byte
+// that names position k at or past len_k (zero padding cannot be wrong), a
+// position the mask leaves out, or no position at all, is left.
+template <int U>
+__device__ __forceinline__ void pq_repair_commit(bcp_pq_repair_result *rec, const v4u (&ps)[U], const v4u (&qs)[U],
+                                                 const_as<bcp_source> *run, uint32_t nsrc,
+                                                 unsigned long long allow, uint64_t pbody, uint64_t qbody,
+                                                 uint64_t off, uint32_t lane_off) {
+  uint32_t first = 0xFFFFFFFFu, np = 0, nq = 0, nboth = 0, nfound = 0, nfixed = 0, nleft = 0;
+  unsigned long long members = 0;
+#pragma unroll
+  for (int u = 0; u < U; u++) {
+#pragma unroll
+    for (int c = 0; c < 4; c++) {
+      const uint32_t hp = nz_bytes(ps[u][c]), hq = nz_bytes(qs[u][c]);
+      const uint64_t j = off + lane_off + (uint32_t)u * 1024u + (uint32_t)c * 4u;  // the dword's stripe offset
+      np += (uint32_t)__builtin_popcount(hp);
+      nq += (uint32_t)__builtin_popcount(hq);
+      nboth += (uint32_t)__builtin_popcount(hp & hq);
+      if (hp & ~hq) {  // (the tail is masked: every flagged byte lies below out_len)
+        members |= BCP_PQ_BAD_P;
+        if (allow & BCP_PQ_BAD_P) nfixed += pq_fix_bytes(pbody + j, hp & ~hq, ps[u][c], 4u);
+        else nleft += (uint32_t)__builtin_popcount(hp & ~hq);
+      }
+      if (hq & ~hp) {
+        members |= BCP_PQ_BAD_Q;
+        if (allow & BCP_PQ_BAD_Q) nfixed += pq_fix_bytes(qbody + j, hq & ~hp, qs[u][c], 4u);
+        else nleft += (uint32_t)__builtin_popcount(hq & ~hp);
+      }
+      if (hp | hq) {
+        const uint32_t o = lane_off + (uint32_t)u * 1024u + (uint32_t)c * 4u + ((uint32_t)__builtin_ctz(hp | hq) >> 3);
+        first = o < first ? o : first;
+      }
+    }
+  }
+  uint32_t nfixed_d = 0;
+#pragma unroll
+  for (int u = 0; u < U; u++) {
+    v4u t = ps[u], both;
+#pragma unroll
+    for (int c = 0; c < 4; c++) both[c] = nz_bytes(ps[u][c]) & nz_bytes(qs[u][c]);
+#pragma unroll 1
+    for (uint32_t k = 0; k < nsrc; k++) {
+      uint32_t hit = 0;
+      const bool may = (allow >> k) & 1ull;
+      const uint64_t ptr = run[k].ptr, len = run[k].len;  // uniform; a (0, 0) source has no byte below len
+#pragma unroll
+      for (int c = 0; c < 4; c++) {
+        const uint32_t h = both[c] & ~nz_bytes(t[c] ^ qs[u][c]);
+        hit += (uint32_t)__builtin_popcount(h);
+        const uint64_t j = off + lane_off + (uint32_t)u * 1024u + (uint32_t)c * 4u;
+        if (h && may && len > j)
+          nfixed_d += pq_fix_bytes(ptr + j, h, ps[u][c], len - j >= 4u ? 4u : (uint32_t)(len - j));
+      }
+      if (hit) members |= 1ull << k;
+      nfound += hit;
+      t = mul2(t);
+    }
+  }
+  if (nfound < nboth) members |= BCP_PQ_BAD_NOWHERE;
+  nleft += nboth - nfixed_d;
+  nfixed += nfixed_d;
+  unsigned long long f = first == 0xFFFFFFFFu ? ~0ull : off + first, cp = np, cq = nq, cf = nfixed, cl = nleft;
+  for (int o = 32; o > 0; o >>= 1) {
+    const unsigned long long fo = __shfl_xor(f, o, 64);
+    f = fo < f ? fo : f;
+    cp += __shfl_xor(cp, o, 64);
+    cq += __shfl_xor(cq, o, 64);
+    cf += __shfl_xor(cf, o, 64);
+    cl += __shfl_xor(cl, o, 64);
+    members |= __shfl_xor(members, o, 64);
+  }
+  if ((threadIdx.x & 63u) == 0 && members) {
+    __hip_atomic_fetch_min((unsigned long long *)&rec->first_bad, f, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    __hip_atomic_fetch_add((unsigned long long *)&rec->p_bad, cp, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    __hip_atomic_fetch_add((unsigned long long *)&rec->q_bad, cq, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    __hip_atomic_fetch_or((unsigned long long *)&rec->members, members, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    __hip_atomic_fetch_add((unsigned long long *)&rec->fixed, cf, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    __hip_atomic_fetch_add((unsigned long long *)&rec->left, cl, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  }
+}
+
+enum PqForm { kPqGen = 0, kPqSolve = 1, kPqCheck = 2, kPqRepair = 3 };
 
 // WIN: the windowed instantiations (PqBatchWin's two more tables, w); a stripe
 // without a window in such a batch has lim = UINT64_MAX on every source and
 // so keeps the plain semantics.  The bodies and the outputs are addressed
 // with plain `off` in both.
-template <int U, PqForm F, bool WIN>
-__device__ __forceinline__ void pq_tile(const PqBatch &b, const PqWinTab &w, uint32_t t, bcp_pq_check_result *res) {
+// R: the form's record, bcp_pq_repair_result for REPAIR.
+template <int U, PqForm F, bool WIN, class R>
+__device__ __forceinline__ void pq_tile(const PqBatch &b, const PqWinTab &w, uint32_t t, R *res) {
   constexpr bool SOLVE = F == kPqSolve;
   constexpr uint32_t T = (uint32_t)kBlock * U * 16u;
   const_as<PqTile> *tr = cst(b.tiles) + t;
@@ -312,7 +421,7 @@ __device__ __forceinline__ void pq_tile(const PqBatch &b, const PqWinTab &w, uin
     case 1: pq_group<1, U, WIN>(p, q, run, wrun, off, offw, T, lane_off); break;
     default: break;
   }
-  if constexpr (F == kPqCheck) {
+  if constexpr (F == kPqCheck || F == kPqRepair) {
 #pragma unroll
     for (int u = 0; u < U; u++) q[u] ^= qb[u];  // p = Ps, q = Qs
     if (out_left < T) {  // the stripe's last tile (uniform)
@@ -323,7 +432,9 @@ __device__ __forceinline__ void pq_tile(const PqBatch &b, const PqWinTab &w, uin
 #pragma unroll
     for (int u = 1; u < U; u++) any |= p[u] | q[u];
     if (__ballot((any[0] | any[1] | any[2] | any[3]) != 0u) == 0) return;  // clean: no store, no atomic
-    pq_check_commit<U>(res + tr->stripe, p, q, d->nsrc, off, lane_off);
+    if constexpr (F == kPqRepair)
+      pq_repair_commit<U>(res + tr->stripe, p, q, run, d->nsrc, d->allow, d->p, d->q, off, lane_off);
+    else pq_check_commit<U>(res + tr->stripe, p, q, d->nsrc, off, lane_off);
   } else if constexpr (SOLVE) {
 #pragma unroll
     for (int u = 0; u < U; u++) q[u] ^= qb[u];  // p = Ps, q = Qs
@@ -346,8 +457,8 @@ __device__ __forceinline__ void pq_tile(const PqBatch &b, const PqWinTab &w, uin
   }
 }
 
-template <int U, PqForm F, bool WIN = false>
-__device__ __forceinline__ void pq_body(const PqBatch &b, bcp_pq_check_result *res, const PqWinTab &w = PqWinTab{}) {
+template <int U, PqForm F, bool WIN = false, class R>
+__device__ __forceinline__ void pq_body(const PqBatch &b, R *res, const PqWinTab &w = PqWinTab{}) {
   // Work queue, one tile per grab (two LDS slots as in stream_body).
   __shared__ uint32_t next[2];
   if (threadIdx.x == 0) next[0] = queue_grab(b.ctr, b.base);
@@ -355,7 +466,7 @@ __device__ __forceinline__ void pq_body(const PqBatch &b, bcp_pq_check_result *r
   uint32_t t = __builtin_amdgcn_readfirstlane(next[0]);
   int slot = 0;
   while (t < b.ntiles) {
-    pq_tile<U, F, WIN>(b, w, t, res);
+    pq_tile<U, F, WIN, R>(b, w, t, res);
     slot ^= 1;
     if (threadIdx.x == 0) next[slot] = queue_grab(b.ctr, b.base);
     __syncthreads();
@@ -365,7 +476,7 @@ __device__ __forceinline__ void pq_body(const PqBatch &b, bcp_pq_check_result *r
 
 template <int U, bool SOLVE>
 __global__ __launch_bounds__(kBlock) void pq_desc(PqBatch b) {
-  pq_body<U, SOLVE ? kPqSolve : kPqGen>(b, nullptr);
+  pq_body<U, SOLVE ? kPqSolve : kPqGen>(b, (bcp_pq_check_result *)nullptr);
 }
 
 // The CHECK form (bcp_pq_check_stripes_async): same tiles, same queue, one
@@ -373,6 +484,13 @@ __global__ __launch_bounds__(kBlock) void pq_desc(PqBatch b) {
 template <int U>
 __global__ __launch_bounds__(kBlock) void pq_check_desc(PqBatch b, bcp_pq_check_result *res) {
   pq_body<U, kPqCheck>(b, res);
+}
+
+// The REPAIR form (bcp_pq_repair_stripes_async): CHECK's batch, the stripes'
+// masks in their records, one bcp_pq_repair_result per stripe (pq_repair_init).
+template <int U>
+__global__ __launch_bounds__(kBlock) void pq_repair_desc(PqBatch b, bcp_pq_repair_result *res) {
+  pq_body<U, kPqRepair>(b, res);
 }
 
 // The windowed forms of all three (the _win entry points): one kernel per
@@ -385,6 +503,11 @@ __global__ __launch_bounds__(kBlock) void pq_win_desc(PqBatchWin b, bcp_pq_check
 __global__ __launch_bounds__(kBlock) void pq_check_init(bcp_pq_check_result *res, uint32_t n) {
   const uint32_t i = blockIdx.x * kBlock + threadIdx.x;
   if (i < n) res[i] = bcp_pq_check_result{~0ull, 0ull, 0ull, 0ull};
+}
+
+__global__ __launch_bounds__(kBlock) void pq_repair_init(bcp_pq_repair_result *res, uint32_t n) {
+  const uint32_t i = blockIdx.x * kBlock + threadIdx.x;
+  if (i < n) res[i] = bcp_pq_repair_result{~0ull, 0ull, 0ull, 0ull, 0ull, 0ull};
 }
 
 hipError_t launch_pq(hipStream_t st, int grid, int vecs, bool solve, const PqBatch &b) {
@@ -425,6 +548,19 @@ hipError_t launch_pq_check(hipStream_t st, int grid, int vecs, const PqBatch &b,
   if (grid <= 0 || !pq_vecs_ok(vecs) || !res) return hipErrorInvalidValue;
   if (vecs == 8) hipLaunchKernelGGL((pq_check_desc<8>), dim3(grid), dim3(kBlock), 0, st, b, res);
   else hipLaunchKernelGGL((pq_check_desc<4>), dim3(grid), dim3(kBlock), 0, st, b, res);
+  return hipGetLastError();
+}
+
+hipError_t launch_pq_repair_init(hipStream_t st, bcp_pq_repair_result *res, uint32_t n) {
+  if (!n) return hipSuccess;
+  hipLaunchKernelGGL(pq_repair_init, dim3((n + kBlock - 1) / kBlock), dim3(kBlock), 0, st, res, n);
+  return hipGetLastError();
+}
+
+hipError_t launch_pq_repair(hipStream_t st, int grid, int vecs, const PqBatch &b, bcp_pq_repair_result *res) {
+  if (grid <= 0 || !pq_vecs_ok(vecs) || !res) return hipErrorInvalidValue;
+  if (vecs == 8) hipLaunchKernelGGL((pq_repair_desc<8>), dim3(grid), dim3(kBlock), 0, st, b, res);
+  else hipLaunchKernelGGL((pq_repair_desc<4>), dim3(grid), dim3(kBlock), 0, st, b, res);
   return hipGetLastError();
 }
 

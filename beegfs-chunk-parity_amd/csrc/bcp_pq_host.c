@@ -1,5 +1,10 @@
 /* bcp_pq_host.c -- host-only pieces of Q parity (no device needed). */
 #include <errno.h>
+#include <fcntl.h>
+#include <string.h>
+#include <sys/stat.h>
+#include <time.h>
+#include <unistd.h>
 
 #include "bcp.h"
 #include "bcp_task.h"
@@ -29,4 +34,67 @@ int bcp_pq_culprit(const bcp_pq_check_result *r, int *position) {
     if (m >> BCP_MAX_SOURCES) return BCP_CULPRIT_MANY; /* bits above 58 are no member */
     if (position) *position = __builtin_ctzll(m);
     return BCP_CULPRIT_DATA;
+}
+
+/* Which members a repair may write (bcp.h). */
+int bcp_pq_repair_verdict(const bcp_pq_check_result *r, uint32_t nsrc, int mode, uint32_t max_members,
+                          uint64_t *allow) {
+    if (!r || !allow || (mode != BCP_REPAIR_PARITY && mode != BCP_REPAIR_ALL)) return -EINVAL;
+    *allow = 0;
+    const uint64_t m = r->members;
+    if (!m) return BCP_VERDICT_CLEAN;
+    const uint64_t data = m & ((1ull << BCP_MAX_SOURCES) - 1);
+    const uint64_t known = data | (m & (BCP_PQ_BAD_P | BCP_PQ_BAD_Q));
+    if (m != known) return BCP_VERDICT_UNLOCATED; /* BAD_NOWHERE, or a bit that is no member */
+    if (nsrc < BCP_MAX_SOURCES && (data >> nsrc)) return BCP_VERDICT_UNLOCATED;
+    if ((uint32_t)__builtin_popcountll(known) > max_members) return BCP_VERDICT_POLICY;
+    if (data && mode == BCP_REPAIR_PARITY) return BCP_VERDICT_POLICY;
+    *allow = known;
+    return BCP_VERDICT_REPAIR;
+}
+
+/* In-place patch of the blocks that differ (bcp.h): decisions 1-3 of
+ * INTEGRATION.md, "Scrub repair". */
+#define PATCH_BLOCK 4096u
+int bcp_patch_file(const char *path, uint64_t body_off, const void *was, const void *now, uint64_t len,
+                   uint64_t expect_size, const struct timespec *expect_mtime, uint64_t *bytes_written) {
+    if (bytes_written) *bytes_written = 0;
+    if (!path || !expect_mtime || (len && (!was || !now))) return -EINVAL;
+    const int fd = open(path, O_WRONLY | O_CLOEXEC);
+    if (fd < 0) return -errno;
+    struct stat sb;
+    int rc = 0;
+    uint64_t total = 0;
+    if (fstat(fd, &sb) != 0) {
+        rc = -errno;
+    } else if ((uint64_t)sb.st_size != expect_size || sb.st_mtim.tv_sec != expect_mtime->tv_sec ||
+               sb.st_mtim.tv_nsec != expect_mtime->tv_nsec) {
+        rc = -ESTALE;
+    } else if (body_off > expect_size || len > expect_size - body_off) {
+        rc = -EINVAL;
+    }
+    const unsigned char *a = (const unsigned char *)was, *b = (const unsigned char *)now;
+    for (uint64_t o = 0; !rc && o < len; o += PATCH_BLOCK) {
+        const uint64_t n = len - o < PATCH_BLOCK ? len - o : PATCH_BLOCK;
+        if (!memcmp(a + o, b + o, n)) continue;
+        uint64_t done = 0;
+        while (done < n) {
+            const ssize_t w = pwrite(fd, b + o + done, n - done, (off_t)(body_off + o + done));
+            if (w < 0 && errno == EINTR) continue;
+            if (w <= 0) {
+                rc = w < 0 ? -errno : -EIO;
+                break;
+            }
+            done += (uint64_t)w;
+        }
+        total += done;
+    }
+    if (total) { /* also after a failed write: what was written keeps the old times */
+        if (fdatasync(fd) != 0 && !rc) rc = -errno;
+        const struct timespec tv[2] = {sb.st_atim, sb.st_mtim};
+        if (futimens(fd, tv) != 0 && !rc) rc = -errno;
+    }
+    if (close(fd) != 0 && !rc) rc = -errno;
+    if (bytes_written) *bytes_written = total;
+    return rc;
 }

@@ -42,7 +42,8 @@
  *       (bcp_pipeline_rebuild2), the paths that cannot be go to --lost FILE and
  *       the exit status is then 1.  --q-windowed (with --also): items past the
  *       window have Q files too and are recovered like the others.
- *   bcp parity-verify [--db DIR] [--bad FILE] [--read PATH] [--q [--culprits FILE] [--q-windowed]]
+ *   bcp parity-verify [--db DIR] [--bad FILE] [--read PATH] [--q [--culprits FILE] [--q-windowed]
+ *                     [--repair parity|all [--repair-members N] [--dry-run] [--repaired FILE]]]
  *                     <store_root> <ntargets>
  *       The scrub (no counterpart in the reference): for every item of the
  *       database (default <root>/st0/db) the batched pipeline reads the chunks
@@ -60,6 +61,17 @@
  *       also lists the items whose Q file is missing or out of order, and
  *       those make the exit status 1 too.  --q-windowed (with --q): items
  *       past the window are expected to have a Q file and are checked with it.
+ *       --repair parity|all (with --q; without it a usage error, exit 2): the
+ *       scrub also corrects what the syndromes blame (bcp_pipeline_repair_q) --
+ *       `parity` only P and Q files, `all` chunks too -- in items that blame
+ *       at most --repair-members N (default 1) files, and writes back the
+ *       4 KiB blocks that changed, file times restored.  --dry-run corrects
+ *       and re-checks on the device and writes nothing; --repaired FILE gets
+ *       "path<TAB>data|p|q<TAB>target<TAB>bytes" per file written.  A third
+ *       summary line has the repair counts.  The first two lines and the lists
+ *       describe the store as found; the exit status is 0 when every mismatch
+ *       was repaired and nothing else is wrong (with --dry-run: as without
+ *       --repair).
  *
  * Items whose path would leave the store (absolute, "..") are skipped and
  * counted as refused; a run with refused items exits 1.
@@ -86,7 +98,8 @@ static int usage(void)
           "       bcp parity-rebuild [--pipeline|--protocol|--procs] [--fold MODE] [--read PATH] [--lanes N]\n"
           "                          [--db DIR] [--corrupt FILE] [--also TARGET] [--lost FILE] [--q-windowed]\n"
           "                          <store_root> <ntargets> <target>\n"
-          "       bcp parity-verify [--db DIR] [--bad FILE] [--read PATH] [--q [--culprits FILE] [--q-windowed]]\n"
+          "       bcp parity-verify [--db DIR] [--bad FILE] [--read PATH] [--q [--culprits FILE] [--q-windowed]\n"
+          "                         [--repair parity|all [--repair-members N] [--dry-run] [--repaired FILE]]]\n"
           "                         <store_root> <ntargets>\n"
           "       engine: --pipeline (default: batched pipeline on every GPU) | --protocol (per-rank\n"
           "               process_task, ranks as threads) | --procs (ranks as processes)\n"
@@ -98,6 +111,9 @@ static int usage(void)
           "            what cannot be rebuilt) apply to the pipeline only\n"
           "       parity-verify --q also reads and checks the Q files and names the wrong file of a mismatch;\n"
           "            --culprits FILE (with --q only) lists path, data|p|q|many and the storage target\n"
+          "            --repair parity|all (with --q only) corrects in place what the syndromes blame: P and Q files,\n"
+          "            or chunks too; at most N files per item (default 1); --dry-run writes nothing; --repaired FILE\n"
+          "            lists path, data|p|q, target and bytes per file written\n"
           "       --q-windowed (pipeline only): Q files for items past the 10 MiB window too; parity-gen (implies\n"
           "            --q; a --q run without it removes those Q files), parity-rebuild --also, parity-verify --q\n",
           stderr);
@@ -462,8 +478,9 @@ static int cmd_rebuild(int argc, char **argv)
 
 static int cmd_verify(int argc, char **argv)
 {
-    const char *db = NULL, *bad = NULL, *culprits = NULL;
-    int i = 0, with_q = 0, q_windowed = 0;
+    const char *db = NULL, *bad = NULL, *culprits = NULL, *repaired = NULL;
+    int i = 0, with_q = 0, q_windowed = 0, repair = 0, dry_run = 0, bad_repair = 0;
+    long members = 1;
     for (; i < argc && argv[i][0] == '-'; i++) {
         if (!strcmp(argv[i], "--db") && i + 1 < argc)
             db = argv[++i];
@@ -475,11 +492,27 @@ static int cmd_verify(int argc, char **argv)
             with_q = 1;
         else if (!strcmp(argv[i], "--q-windowed"))
             q_windowed = 1;
+        else if (!strcmp(argv[i], "--repair") && i + 1 < argc) {
+            i++;
+            repair = !strcmp(argv[i], "parity") ? BCP_REPAIR_PARITY : !strcmp(argv[i], "all") ? BCP_REPAIR_ALL : 0;
+            bad_repair |= !repair;
+        } else if (!strcmp(argv[i], "--repair-members") && i + 1 < argc) {
+            char *end;
+            members = strtol(argv[++i], &end, 10);
+            bad_repair |= *end || members < 1 || members > MAX_STORAGE_TARGETS + 2;
+        } else if (!strcmp(argv[i], "--dry-run"))
+            dry_run = 1;
+        else if (!strcmp(argv[i], "--repaired") && i + 1 < argc)
+            repaired = argv[++i];
         else if (!strcmp(argv[i], "--read") && i + 1 < argc) {
             if ((g_read_mode = read_mode_arg(argv[++i])) < 0)
                 return usage();
         } else
             return usage();
+    }
+    if (bad_repair || (repair && !with_q) || ((members != 1 || dry_run || repaired) && !repair)) {
+        usage();
+        return 2;
     }
     if (argc - i != 2 || ((culprits || q_windowed) && !with_q))
         return usage();
@@ -498,8 +531,10 @@ static int cmd_verify(int argc, char **argv)
     size_t n = 0;
     bcp_verify_stats vs;
     bcp_verify_q_stats qs;
+    bcp_repair_q_stats rs;
     memset(&vs, 0, sizeof(vs));
     memset(&qs, 0, sizeof(qs));
+    memset(&rs, 0, sizeof(rs));
     int rc = stat(db, &sb) == 0 ? 0 : -errno;
     if (!rc)
         rc = bcp_pdb_open(db, DB_VERSION, &pdb);
@@ -512,7 +547,12 @@ static int cmd_verify(int argc, char **argv)
         rc = pipeline_on_all_gpus(&pl, 0);
         if (!rc && q_windowed)
             rc = bcp_pipeline_set_q_windowed(pl, 1);
-        if (!rc && with_q) {
+        if (!rc && repair) {
+            rc = bcp_pipeline_repair_q(pl, root, ntargets, items, n, repair, (uint32_t)members, dry_run, NULL, bad,
+                                       culprits, repaired, stderr, &rs);
+            qs = rs.q;
+            vs = qs.v;
+        } else if (!rc && with_q) {
             rc = bcp_pipeline_verify_q(pl, root, ntargets, items, n, NULL, bad, culprits, stderr, &qs);
             vs = qs.v;
         } else if (!rc)
@@ -534,6 +574,16 @@ static int cmd_verify(int argc, char **argv)
                (unsigned long long)qs.q_checked, (unsigned long long)qs.q_none, (unsigned long long)qs.q_bad,
                (unsigned long long)qs.culprit_data, (unsigned long long)qs.culprit_p,
                (unsigned long long)qs.culprit_q, (unsigned long long)qs.culprit_many);
+    if (repair) {
+        printf("repair (%s%s): %llu done, %llu dry, %llu policy, %llu unlocated, %llu changed, %llu failed; "
+               "%llu files, %llu bytes written, %llu launches\n",
+               repair == BCP_REPAIR_ALL ? "all" : "parity", dry_run ? ", dry run" : "", (unsigned long long)rs.done,
+               (unsigned long long)rs.dry, (unsigned long long)rs.policy, (unsigned long long)rs.unlocated,
+               (unsigned long long)rs.changed, (unsigned long long)rs.failed, (unsigned long long)rs.files_written,
+               (unsigned long long)rs.bytes_written, (unsigned long long)rs.repair_launches);
+        if (!dry_run) /* a mismatch that was repaired is no longer one */
+            return (vs.no_parity || qs.q_bad || vs.size || vs.mismatch != rs.done || vs.refused || vs.errors) ? 1 : 0;
+    }
     return (vs.no_parity || qs.q_bad || vs.size || vs.mismatch || vs.refused || vs.errors) ? 1 : 0;
 }
 

@@ -53,7 +53,9 @@ extern "C" {
  * bcp_pq_check_stripes_async / bcp_pq_check_result / bcp_pq_culprit and the
  * "last_desc_form" value 6; Q parity over window replay,
  * bcp_pq_stripes_win_async / bcp_pq_recover_stripes_win_async /
- * bcp_pq_check_stripes_win_async and the "last_desc_form" values 7, 8 and 9.
+ * bcp_pq_check_stripes_win_async and the "last_desc_form" values 7, 8 and 9;
+ * the scrub repair's bcp_pq_repair_stripes_async / bcp_pq_repair_result /
+ * bcp_pq_repair_verdict / bcp_patch_file and the "last_desc_form" value 10.
  * 3 (r05): the pipeline's MAP read mode (BCP_READ_MAP), its
  * bcp_pipeline_timing fields and bcp_host_register_dma_src removed.
  * 2 (r04): bcp_task.h's bcp_run_stats gained `refused`, bcp_pipeline_opts
@@ -248,6 +250,36 @@ typedef struct bcp_pq_check_result {
 int bcp_pq_check_stripes_async(bcp_queue *q, const bcp_stripe *stripes, uint32_t nstripes,
                                const bcp_source *sources, uint32_t nsources,
                                const uint64_t *q_body, bcp_pq_check_result *results_dev);
+
+/* One record per stripe of a repair (bcp_pq_repair_stripes_async): the four
+ * fields of bcp_pq_check_result with the same meaning -- the state as found,
+ * before anything was corrected -- and two byte counts.  fixed + left is the
+ * number of j with Ps[j] or Qs[j] non-zero. */
+typedef struct bcp_pq_repair_result {
+    uint64_t first_bad, p_bad, q_bad, members;
+    uint64_t fixed;      /* bad bytes corrected in place */
+    uint64_t left;       /* bad bytes not touched */
+} bcp_pq_repair_result;
+/* bcp_pq_check_stripes_async that also corrects, in place in device memory,
+ * the bad bytes whose member allow[s] (nstripes masks, required; bit layout of
+ * `members`) admits.  For a bad byte j < out_len:
+ *   Ps != 0, Qs == 0: P[j] ^= Ps when allow has BAD_P;
+ *   Ps == 0, Qs != 0: Q[j] ^= Qs when allow has BAD_Q;
+ *   both != 0:        D_k[j] ^= Ps for the k < nsrc with g^k * Ps = Qs, when
+ *                     allow has bit k and j < len_k;
+ * every other bad byte is left: no such k, a member the mask leaves out, or
+ * j at or past len_k (zero padding cannot be wrong; a (0, 0) source is never
+ * dereferenced).  Validation is the check's, window must be 0.  The sources
+ * and both bodies are written as well as read, so across the whole batch they
+ * must not overlap one another: a byte corrected for one stripe must not be a
+ * byte another stripe, or another member of the same stripe, reads.  Nothing
+ * is written at or past len_k or out_len.  results_dev: nstripes records,
+ * fully written, {UINT64_MAX, 0, 0, 0, 0, 0} for a clean stripe.  The
+ * correction is single-error per byte offset: two members wrong at the same j
+ * can name a third ("Scrub repair"). */
+int bcp_pq_repair_stripes_async(bcp_queue *q, const bcp_stripe *stripes, uint32_t nstripes,
+                                const bcp_source *sources, uint32_t nsources, const uint64_t *q_body,
+                                const uint64_t *allow, bcp_pq_repair_result *results_dev);
 /* ---- P + Q over window replay ------------------------------------------ */
 /* The three entry points above for stripes with a window W.  The replayed
  * stream of source k (quirk A3-q1, see the top of this file) is a function of
@@ -287,6 +319,36 @@ int bcp_pq_check_stripes_win_async(bcp_queue *q, const bcp_stripe *stripes, uint
 #define BCP_CULPRIT_Q    3
 #define BCP_CULPRIT_MANY 4   /* more than one bit, or BAD_NOWHERE: not a single-member fault */
 int bcp_pq_culprit(const bcp_pq_check_result *r, int *position);
+
+/* Which members of a record a repair may write under a policy (pure host
+ * arithmetic).  mode: BCP_REPAIR_PARITY, only P and Q; BCP_REPAIR_ALL, data
+ * members too.  Returns BCP_VERDICT_REPAIR with *allow = the record's member
+ * bits, or, with *allow = 0, BCP_VERDICT_CLEAN (members == 0),
+ * BCP_VERDICT_UNLOCATED (BAD_NOWHERE is set, or a data bit at or above nsrc)
+ * or BCP_VERDICT_POLICY (more than max_members member bits, or a data bit
+ * under PARITY).  -EINVAL for a null record or allow, or a mode that is
+ * neither. */
+#define BCP_REPAIR_PARITY 1
+#define BCP_REPAIR_ALL    2
+#define BCP_VERDICT_CLEAN     0
+#define BCP_VERDICT_REPAIR    1
+#define BCP_VERDICT_UNLOCATED 2
+#define BCP_VERDICT_POLICY    3
+int bcp_pq_repair_verdict(const bcp_pq_check_result *r, uint32_t nsrc, int mode, uint32_t max_members,
+                          uint64_t *allow);
+/* Patch a file in place from two images of its body: every 4 KiB block of
+ * [0, len) (block boundaries relative to the body) in which now[] differs from
+ * was[] is pwritten from now[] at file offset body_off + block, clipped to len.
+ * The file is opened and fstat'ed first: a size other than expect_size or an
+ * mtime other than *expect_mtime is -ESTALE and nothing is written.  After the
+ * last pwrite and an fdatasync, futimens puts back the atime and mtime that
+ * fstat showed.  Nothing is created, truncated or resized (-EINVAL when
+ * body_off + len exceeds the size).  *bytes_written (may be null) is the sum
+ * of the blocks written; no differing block is success with 0 and the file is
+ * not written at all.  Other failures are -errno (-ENOENT for a missing file). */
+struct timespec;
+int bcp_patch_file(const char *path, uint64_t body_off, const void *was, const void *now, uint64_t len,
+                   uint64_t expect_size, const struct timespec *expect_mtime, uint64_t *bytes_written);
 
 /* Storage target of an item's Q file (pure host arithmetic, no device):
  * `locations` as in bcp_task.h's FileInfo (bits 0..55 chunk holders, bits
@@ -409,7 +471,8 @@ int bcp_set_option(bcp_engine *eng, const char *key, int value);
  * 5 = its recovery form, bcp_pq_recover_stripes_async, 6 = its syndrome
  * form, bcp_pq_check_stripes_async, 7 / 8 / 9 = the windowed kernels of
  * bcp_pq_stripes_win_async / bcp_pq_recover_stripes_win_async /
- * bcp_pq_check_stripes_win_async, taken by a batch with a windowed stripe). */
+ * bcp_pq_check_stripes_win_async, taken by a batch with a windowed stripe,
+ * 10 = the repair form, bcp_pq_repair_stripes_async). */
 int bcp_get_option(bcp_engine *eng, const char *key, int *value);
 /* Timer slots for bcp_queue_mark / bcp_queue_elapsed_ms. */
 #define BCP_TIMER_SLOTS 64

@@ -720,6 +720,48 @@ typedef struct { bcp_verify_stats v; uint64_t q_checked, q_none, q_bad,
 int bcp_pipeline_verify_q(bcp_pipeline *pl, const char *store_root, int ntargets, const bcp_work_item *items,
                           size_t nitems, bcp_verify_q_item *results, const char *bad_list_path,
                           const char *culprit_list_path, FILE *log, bcp_verify_q_stats *stats);
+/* Scrub repair (added under ABI 4; INTEGRATION.md, "Scrub repair"): a
+ * bcp_pipeline_verify_q run -- the same launches, records, verdicts and lists
+ * for the store as found -- that also corrects what the syndromes blame.  The
+ * MISMATCH items of a batch whose record passes the policy
+ * (bcp_pq_repair_verdict with mode BCP_REPAIR_PARITY or BCP_REPAIR_ALL and
+ * max_members >= 1) go into one more, small launch while the batch is still on
+ * the device (bcp_pq_repair_stripes_async), are checked again there
+ * (bcp_pq_check_stripes_async) and, when that record is clean, written back
+ * with bcp_patch_file: only the 4 KiB blocks that changed, into the existing
+ * files, atime and mtime put back.  A slot is not reused before the repairs of
+ * its items are written.  Per item: */
+#define BCP_REPAIRED_NONE      0  /* not a MISMATCH: nothing to do */
+#define BCP_REPAIRED_DONE      1  /* corrected, checked and written */
+#define BCP_REPAIRED_DRY       2  /* dry_run: corrected on the device and checked clean, nothing written */
+#define BCP_REPAIRED_POLICY    3  /* refused by the policy */
+#define BCP_REPAIRED_UNLOCATED 4  /* BAD_NOWHERE, bytes left uncorrected, q_state not CHECKED, or windowed */
+#define BCP_REPAIRED_CHANGED   5  /* a file's size or mtime is not what the batch's stat saw: nothing written */
+#define BCP_REPAIRED_FAILED    6  /* the second check was not clean, or a write failed; counts in errors */
+typedef struct {
+    uint32_t status, q_state, culprit; /* bcp_verify_q_item, field for field: the store as found */
+    int32_t  target;
+    uint64_t first_bad, p_bad, q_bad;
+    uint32_t repair;       /* BCP_REPAIRED_* */
+    uint32_t reserved;
+    uint64_t bytes_fixed;  /* DONE, DRY: bytes the device corrected */
+} bcp_repair_q_item;
+typedef struct {
+    bcp_verify_q_stats q;  /* what bcp_pipeline_verify_q reports for the same store (errors: plus FAILED items) */
+    uint64_t none, done, dry, policy, unlocated, changed, failed; /* items per BCP_REPAIRED_* */
+    uint64_t files_written, bytes_written; /* bytes: the sum of the blocks written */
+    uint64_t repair_launches;              /* 0 on a clean store */
+} bcp_repair_q_stats;
+/* results (or NULL), the bad list and the culprit list are those of
+ * bcp_pipeline_verify_q.  repaired_list_path (or NULL; created and truncated)
+ * receives one line per file written, in the order written:
+ * path<TAB>data|p|q<TAB>target<TAB>bytes written.  With max_members > 1 every
+ * allowed member of an item is written; a failed write makes the item FAILED.
+ * -EINVAL for a mode that is neither or max_members 0. */
+int bcp_pipeline_repair_q(bcp_pipeline *pl, const char *store_root, int ntargets, const bcp_work_item *items,
+                          size_t nitems, int mode, uint32_t max_members, int dry_run, bcp_repair_q_item *results,
+                          const char *bad_list_path, const char *culprit_list_path, const char *repaired_list_path,
+                          FILE *log, bcp_repair_q_stats *stats);
 /* ---- Q parity (a second, Reed-Solomon parity per item; added under ABI 4) --
  * With Q on, bcp_pipeline_run and bcp_gen_round_pipeline also write, per item,
  *   <root>/st<q>/parityq/<path>,  q = bcp_q_target(locations, ntargets):
