@@ -230,6 +230,11 @@ _SIGS = {
     "bcp_pq_repair_stripes_async": ([_V, ctypes.POINTER(Stripe), ctypes.c_uint32, ctypes.POINTER(Source),
                                      ctypes.c_uint32, ctypes.POINTER(ctypes.c_uint64),
                                      ctypes.POINTER(ctypes.c_uint64), _V], ctypes.c_int),
+    "bcp_pq_repair_stripes_win_async": ([_V, ctypes.POINTER(Stripe), ctypes.c_uint32, ctypes.POINTER(Source),
+                                         ctypes.c_uint32, ctypes.POINTER(ctypes.c_uint64),
+                                         ctypes.POINTER(ctypes.c_uint64), _V], ctypes.c_int),
+    "bcp_pq_repair_win_phases": ([ctypes.POINTER(Stripe), ctypes.POINTER(Source), ctypes.c_uint64,
+                                  ctypes.POINTER(ctypes.c_uint64), ctypes.c_uint32], ctypes.c_int),
     "bcp_pq_repair_verdict": ([ctypes.POINTER(PqCheckResult), ctypes.c_uint32, ctypes.c_int, ctypes.c_uint32,
                                ctypes.POINTER(ctypes.c_uint64)], ctypes.c_int),
     "bcp_patch_file": ([ctypes.c_char_p, ctypes.c_uint64, _V, _V, ctypes.c_uint64, ctypes.c_uint64,
@@ -310,6 +315,7 @@ _SIGS = {
                                ctypes.POINTER(VerifyQStats)], ctypes.c_int),
     "bcp_pipeline_set_q_parity": ([_V, ctypes.c_int], ctypes.c_int),
     "bcp_pipeline_set_q_windowed": ([_V, ctypes.c_int], ctypes.c_int),
+    "bcp_pipeline_set_repair_windowed": ([_V, ctypes.c_int], ctypes.c_int),
     "bcp_pipeline_q_stats": ([_V, ctypes.POINTER(ctypes.c_uint64), ctypes.POINTER(ctypes.c_uint64),
                               ctypes.POINTER(ctypes.c_uint64)], ctypes.c_int),
     "bcp_pipeline_rebuild2": ([_V, ctypes.c_char_p, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.POINTER(WorkItem),
@@ -421,6 +427,19 @@ def pq_repair_verdict(result, nsrc: int, mode: int, max_members: int = 1) -> tup
     if v < 0:
         raise BcpError("bcp_pq_repair_verdict", v)
     return v, allow.value
+
+
+def pq_repair_win_phases(out_len: int, window: int, lens, allow: int, cap: int = MAX_SOURCES) -> tuple:
+    """bcp_pq_repair_win_phases: (number of phases, [thresholds]) of a windowed repair of one stripe whose
+    sources have the lengths `lens` (position order) under the mask `allow`; at most `cap` thresholds come
+    back.  BcpError -EINVAL for a window that is neither 0 nor a multiple of 32768 or more than 56 sources."""
+    st = Stripe(0, out_len, 0, len(lens), window)
+    so = (Source * max(len(lens), 1))(*[Source(0, int(n)) for n in lens])
+    bounds = (ctypes.c_uint64 * max(cap, 1))()
+    n = lib().bcp_pq_repair_win_phases(ctypes.byref(st), so, allow, bounds, cap)
+    if n < 0:
+        raise BcpError("bcp_pq_repair_win_phases", n)
+    return n, [int(x) for x in bounds[:min(n - 1, cap)]]
 
 
 def patch_file(path: str, body_off: int, was, now, expect_size: int, expect_mtime_ns: int) -> int:
@@ -609,15 +628,18 @@ class Queue:
         call("bcp_pq_check_stripes_win_async" if windowed else "bcp_pq_check_stripes_async", self.h, st,
              len(stripes), so, len(sources), qb, _V(results_ptr))
 
-    def pq_repair(self, stripes, sources, q_body, allow, results_ptr: int):
+    def pq_repair(self, stripes, sources, q_body, allow, results_ptr: int, windowed=False):
         """pq_check that also corrects in place the bad bytes whose member allow[s] admits (bit layout of
         PqCheckResult.members; None: the null pointer); the sources and bodies are written, so stripes
-        must not share them.  results_ptr: device memory for len(stripes) PqRepairResult records."""
+        must not share them.  results_ptr: device memory for len(stripes) PqRepairResult records.
+        windowed: bcp_pq_repair_stripes_win_async, where a stripe's window may be a multiple of 32768 and
+        the batch runs in phases (engine key last_pq_repair_phases)."""
         st = (Stripe * max(len(stripes), 1))(*[Stripe(*s) for s in stripes])
         so = (Source * max(len(sources), 1))(*[Source(*s) for s in sources])
         qb = (ctypes.c_uint64 * max(len(q_body), 1))(*q_body)
         al = None if allow is None else (ctypes.c_uint64 * max(len(allow), 1))(*allow)
-        call("bcp_pq_repair_stripes_async", self.h, st, len(stripes), so, len(sources), qb, al, _V(results_ptr))
+        call("bcp_pq_repair_stripes_win_async" if windowed else "bcp_pq_repair_stripes_async", self.h, st,
+             len(stripes), so, len(sources), qb, al, _V(results_ptr))
 
     def fill_synthetic(self, dptr: int, nbytes: int, seed: int, byte_offset: int = 0):
         call("bcp_dev_fill_synthetic_async", self.h, _V(dptr), nbytes, seed, byte_offset)
@@ -1012,6 +1034,11 @@ class Pipeline:
         """Items past the 10 MiB window have Q files too (run with Q on, rebuild2, verify_q); off by
         default.  `on` goes through as it is: anything but 0 or 1 is -EINVAL."""
         call("bcp_pipeline_set_q_windowed", self.h, int(on))
+
+    def set_repair_windowed(self, on: bool):
+        """repair_q also repairs items past the 10 MiB window (needs set_q_windowed); off by default:
+        they are UNLOCATED.  `on` goes through as it is: anything but 0 or 1 is -EINVAL."""
+        call("bcp_pipeline_set_repair_windowed", self.h, int(on))
 
     def q_stats(self) -> dict:
         """Q files of the last run: written, and items left with P only (no Q target / windowed)."""

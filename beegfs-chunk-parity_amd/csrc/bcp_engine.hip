@@ -42,7 +42,8 @@ struct bcp_engine {
   pthread_mutex_t lock = PTHREAD_MUTEX_INITIALIZER;
   std::atomic<int> last_stream_vecs{0};  // U of the latest xor_stream launch (tools)
   std::atomic<int> last_desc_vecs{0};    // U of the latest descriptor-kernel launch (tools)
-  std::atomic<int> last_desc_form{0};    // 1 xor_desc (desc_tiles), 2 xor_desc_args, 3 check_desc, 4 / 5 / 6 pq_desc gen / solve / check, 7 / 8 / 9 their windowed forms, 10 pq_repair_desc
+  std::atomic<int> last_desc_form{0};    // 1 xor_desc (desc_tiles), 2 xor_desc_args, 3 check_desc, 4 / 5 / 6 pq_desc gen / solve / check, 7 / 8 / 9 their windowed forms, 10 pq_repair_desc, 11 pq_repair_win_desc
+  std::atomic<int> last_pq_repair_phases{0};  // launches of the latest bcp_pq_repair_stripes_win_async
 };
 
 namespace {
@@ -389,6 +390,7 @@ extern "C" int bcp_get_option(bcp_engine *eng, const char *key, int *value) {
   else if (!strcmp(key, "last_stream_vecs")) *value = eng->last_stream_vecs.load(std::memory_order_relaxed);
   else if (!strcmp(key, "last_desc_vecs")) *value = eng->last_desc_vecs.load(std::memory_order_relaxed);
   else if (!strcmp(key, "last_desc_form")) *value = eng->last_desc_form.load(std::memory_order_relaxed);
+  else if (!strcmp(key, "last_pq_repair_phases")) *value = eng->last_pq_repair_phases.load(std::memory_order_relaxed);
   else rc = -EINVAL;
   pthread_mutex_unlock(&eng->lock);
   return rc;
@@ -1226,7 +1228,9 @@ const Gf256 g_gf;
 // with `check` (nstripes device records, initialised on the queue first)
 // read beside the P bodies at dst (CHECK).  `repair` with `allow` is the
 // REPAIR form: CHECK's batch and validation, its own records, the stripes'
-// masks in their table records, never windowed.
+// masks in their table records; with `win` and a windowed stripe its tiles are
+// ordered by (phase, stripe, subtile) and each phase is a launch of its own
+// (bcp_pq_repair_win_phases is the rule).
 // The staged tables are the stripes' records, their source runs copied in the
 // caller's order, and one record per tile; they go through stage_tables with
 // the pointer-table threshold, since the kernel reads them once per tile.
@@ -1278,6 +1282,7 @@ static int submit_pq(bcp_queue *q, const bcp_stripe *stripes, uint32_t nstripes,
     if (q->broken) return -EIO;
     (void)hipGetLastError();
     HIP_RC(launch_pq_repair_init(q->stream, repair, nstripes));
+    if (win) e->last_pq_repair_phases.store(0, std::memory_order_relaxed);
   }
   if (tiles8 == 0) return 0;
   int vecs = e->tuning.desc_vecs;
@@ -1368,6 +1373,43 @@ static int submit_pq(bcp_queue *q, const bcp_stripe *stripes, uint32_t nstripes,
       }
     }
   });
+  // windowed REPAIR: a source's echo tiles run after its home tiles (bcp.h).  phase_end[p] is where
+  // phase p's tiles end in the reordered tables.
+  std::vector<uint32_t> phase_end;
+  if (repair && windowed) {
+    std::vector<uint8_t> ph(ntiles);
+    uint32_t nph = 1;
+    for (uint32_t i = 0; i < nstripes; i++) {
+      uint64_t bound[BCP_MAX_SOURCES];
+      const bcp_stripe &s = stripes[i];
+      const int np = bcp_pq_repair_win_phases(&s, s.nsrc ? sources + s.first_src : nullptr, allow[i], bound,
+                                              BCP_MAX_SOURCES);
+      if (np < 1) return -EINVAL;  // (validated above: not reached)
+      const uint32_t n = (uint32_t)tiles_of(i);
+      uint32_t p = 0;
+      for (uint32_t j = 0; j < n; j++) {
+        while (p + 1 < (uint32_t)np && bound[p] <= (uint64_t)j * T) p++;
+        ph[tile0[i] + j] = (uint8_t)p;
+      }
+      nph = std::max(nph, (uint32_t)np);
+    }
+    phase_end.assign(nph, 0);
+    for (uint32_t t = 0; t < ntiles; t++) phase_end[ph[t]]++;
+    std::vector<uint32_t> at(nph);
+    uint32_t acc = 0;
+    for (uint32_t p = 0; p < nph; p++) {
+      at[p] = acc;
+      acc += phase_end[p];
+      phase_end[p] = acc;
+    }
+    const std::vector<PqTile> tiles(ht, ht + ntiles);
+    const std::vector<uint64_t> offws(hoffw, hoffw + ntiles);
+    for (uint32_t t = 0; t < ntiles; t++) {  // stable: (stripe, subtile) order inside a phase
+      const uint32_t to = at[ph[t]]++;
+      ht[to] = tiles[t];
+      hoffw[to] = offws[t];
+    }
+  }
   char *d = nullptr;
   if ((rc = stage_tables(q, slot, bytes, (size_t)e->tuning.table_host_max, &d))) return rc;
   PqBatch b;
@@ -1386,6 +1428,33 @@ static int submit_pq(bcp_queue *q, const bcp_stripe *stripes, uint32_t nstripes,
   if ((uint32_t)grid > ntiles) grid = (int)ntiles;
   if (q->broken) return -EIO;
   (void)hipGetLastError();  // see launch_stream
+  if (repair && windowed) {
+    uint32_t lo = 0;
+    int launches = 0;
+    for (const uint32_t hi : phase_end) {
+      const uint32_t n = hi - lo;
+      if (!n) continue;
+      PqBatchWin pw = bw;
+      pw.b.tiles += lo;
+      pw.w.offw += lo;
+      pw.b.ntiles = n;
+      pw.b.base = q->qbase;
+      const int g = (uint32_t)grid > n ? (int)n : grid;
+      const hipError_t le = launch_pq_repair_win(q->stream, g, vecs, pw, repair);
+      if ((rc = queue_launched(q, le, (uint64_t)n + (uint64_t)g))) {
+        if (launches && hipEventRecord(slot->done, q->stream) == hipSuccess) slot->used = true;  // earlier phases read the slot
+        return rc;
+      }
+      launches++;
+      lo = hi;
+    }
+    e->last_desc_vecs.store(vecs, std::memory_order_relaxed);
+    e->last_desc_form.store(11, std::memory_order_relaxed);
+    e->last_pq_repair_phases.store(launches, std::memory_order_relaxed);
+    HIP_RC(hipEventRecord(slot->done, q->stream));
+    slot->used = true;
+    return 0;
+  }
   const int form = check ? 2 : lost ? 1 : 0;
   const hipError_t le = repair     ? launch_pq_repair(q->stream, grid, vecs, b, repair)
                         : windowed ? launch_pq_win(q->stream, grid, vecs, form, bw, check)
@@ -1394,6 +1463,7 @@ static int submit_pq(bcp_queue *q, const bcp_stripe *stripes, uint32_t nstripes,
   if (le == hipSuccess) {
     e->last_desc_vecs.store(vecs, std::memory_order_relaxed);
     e->last_desc_form.store(repair ? 10 : (windowed ? 7 : 4) + form, std::memory_order_relaxed);
+    if (repair && win) e->last_pq_repair_phases.store(1, std::memory_order_relaxed);
   }
   if ((rc = queue_launched(q, le, (uint64_t)ntiles + (uint64_t)grid))) return rc;
   HIP_RC(hipEventRecord(slot->done, q->stream));
@@ -1468,6 +1538,18 @@ extern "C" int bcp_pq_check_stripes_win_async(bcp_queue *q, const bcp_stripe *st
   int rc = set_device(q->eng);
   if (rc) return rc;
   return submit_pq(q, stripes, nstripes, sources, nsources, q_body, nullptr, results_dev, true);
+}
+
+// The repair over window replay (bcp.h): a batch with a window runs in phases.
+extern "C" int bcp_pq_repair_stripes_win_async(bcp_queue *q, const bcp_stripe *stripes, uint32_t nstripes,
+                                               const bcp_source *sources, uint32_t nsources,
+                                               const uint64_t *q_body, const uint64_t *allow,
+                                               bcp_pq_repair_result *results_dev) {
+  if (!q || !stripes || !q_body || !allow || !results_dev || (nsources && !sources)) return -EINVAL;
+  if (!nstripes) return 0;
+  int rc = set_device(q->eng);
+  if (rc) return rc;
+  return submit_pq(q, stripes, nstripes, sources, nsources, q_body, nullptr, nullptr, true, allow, results_dev);
 }
 
 extern "C" int bcp_xor_strided_async(bcp_queue *q, void *dst, uint64_t dst_stride, const void *src,

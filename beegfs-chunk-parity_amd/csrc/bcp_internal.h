@@ -341,6 +341,10 @@ struct PqBatchWin {
 // form 0 GEN, 1 SOLVE, 2 CHECK (res required for CHECK only); accounting as launch_pq.
 hipError_t launch_pq_win(hipStream_t st, int grid, int vecs, int form, const PqBatchWin &b,
                          bcp_pq_check_result *res);
+// Windowed REPAIR (bcp_pq_repair_stripes_win_async): one launch per phase, b's
+// tiles and offw pointing at that phase's part of the tables, which the host
+// orders by (phase, stripe, subtile); accounting as launch_pq per launch.
+hipError_t launch_pq_repair_win(hipStream_t st, int grid, int vecs, const PqBatchWin &b, bcp_pq_repair_result *res);
 
 // Kernel launchers (bcp_kernels.hip).  All return hipError_t.
 // Streaming fold.  Consumes ceil(ntiles / grab) + grid counts of a.ctr; the

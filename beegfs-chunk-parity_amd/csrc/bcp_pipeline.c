@@ -45,7 +45,9 @@
  * batch's completion, before the slot is released: the MISMATCH items the
  * policy admits go through bcp_pq_repair_stripes_async and a second check on
  * the slot's device slab, on a queue of the completion thread's own, and the
- * blocks that changed are patched into the files (repair_batch).
+ * blocks that changed are patched into the files (repair_batch).  Items past
+ * the window are admitted only under bcp_pipeline_set_repair_windowed; their
+ * stripes carry the window and both calls are the _win entry points'.
  *
  * Q parity (bcp_pipeline_set_q_parity, bcp_pipeline_rebuild2; bcp_task.h): a
  * task may have a second output, placed after the first in the output slab
@@ -378,6 +380,7 @@ static uint64_t read_extent(const task *t, int k, int direct)
  * completion thread touches them while the run is on. */
 typedef struct repair_ctx {
     int mode, dry_run;
+    int windowed;           /* bcp_pipeline_set_repair_windowed: windowed items are admitted */
     uint32_t max_members;
     bcp_repair_q_item *res; /* per work item: repair, bytes_fixed */
     int list_fd;            /* the repaired list (or -1) */
@@ -896,7 +899,7 @@ static void repair_batch(const complete_arg *a)
             continue;
         bcp_repair_q_item *v = &R->res[t->item];
         v->repair = BCP_REPAIRED_UNLOCATED;
-        if (!t->vq || t->q_state != BCP_QSTATE_CHECKED || t->max_cs > WINDOW)
+        if (!t->vq || t->q_state != BCP_QSTATE_CHECKED || (t->max_cs > WINDOW && !R->windowed))
             continue;
         const bcp_pq_check_result r = {t->first_bad, t->bad_bytes, t->q_bad, t->members};
         const int vd = bcp_pq_repair_verdict(&r, (uint32_t)t->parity_src, R->mode, R->max_members, &t->allow);
@@ -919,12 +922,15 @@ static void repair_batch(const complete_arg *a)
     int rc = st && so && qb && h ? bcp_dev_alloc(a->eng, n * rec, &d) : -ENOMEM;
     if (!rc) {
         uint32_t j = 0, s = 0;
+        int win = 0; /* a windowed stripe among them: the _win entry points, which take a mixed batch */
         for (size_t i = a->first; i < a->last; i++) {
             const task *t = &a->tasks[i];
             if (t->status != BCP_VERIFY_MISMATCH || R->res[t->item].repair != REPAIR_PENDING)
                 continue;
             const int nfold = t->parity_src;
-            st[j] = (bcp_stripe){(uint64_t)a->S->d_in + data_off(t, nfold, a->dir), t->out_len, s, (uint32_t)nfold, 0};
+            st[j] = (bcp_stripe){(uint64_t)a->S->d_in + data_off(t, nfold, a->dir), t->out_len, s, (uint32_t)nfold,
+                                 t->max_cs > WINDOW ? WINDOW : 0};
+            win |= t->max_cs > WINDOW;
             qb[j] = (uint64_t)a->S->d_in + data_off(t, t->q_src, a->dir);
             al[j] = t->allow;
             for (int k = 0; k < nfold; k++)
@@ -933,8 +939,10 @@ static void repair_batch(const complete_arg *a)
         }
         bcp_pq_repair_result *d_rep = d;
         bcp_pq_check_result *d_chk = (bcp_pq_check_result *)(d_rep + n);
-        if (!(rc = bcp_pq_repair_stripes_async(a->qr, st, (uint32_t)n, so, s, qb, al, d_rep)) &&
-            !(rc = bcp_pq_check_stripes_async(a->qr, st, (uint32_t)n, so, s, qb, d_chk)) &&
+        if (!(rc = win ? bcp_pq_repair_stripes_win_async(a->qr, st, (uint32_t)n, so, s, qb, al, d_rep)
+                       : bcp_pq_repair_stripes_async(a->qr, st, (uint32_t)n, so, s, qb, al, d_rep)) &&
+            !(rc = win ? bcp_pq_check_stripes_win_async(a->qr, st, (uint32_t)n, so, s, qb, d_chk)
+                       : bcp_pq_check_stripes_async(a->qr, st, (uint32_t)n, so, s, qb, d_chk)) &&
             !(rc = bcp_d2h_async(a->qr, h, d, n * rec)))
             rc = bcp_queue_sync(a->qr);
         R->launches++;
@@ -1085,6 +1093,7 @@ struct bcp_pipeline {
     size_t desc_cap;    /* stripes the descriptor arrays hold */
     int q_on;           /* bcp_pipeline_set_q_parity */
     int q_win;          /* bcp_pipeline_set_q_windowed */
+    int repair_win;     /* bcp_pipeline_set_repair_windowed */
     uint64_t q_written, q_no_target, q_windowed; /* of the last run */
     repair_ctx *repair; /* during a repair run (bcp_pipeline_repair_q) */
     uint8_t *r2_unrec;  /* during a rebuild2 run: per item, 1 = unrecoverable after the stat phase */
@@ -2253,7 +2262,7 @@ int bcp_pipeline_repair_q(bcp_pipeline *pl, const char *store_root, int ntargets
         return rc;
     bcp_repair_q_item *res = results ? results : calloc(nitems ? nitems : 1, sizeof(*res));
     bcp_verify_q_item *vq = calloc(nitems ? nitems : 1, sizeof(*vq));
-    repair_ctx R = {mode, dry_run != 0, max_members, res, -1, 0, 0, 0, 0};
+    repair_ctx R = {mode, dry_run != 0, pl->repair_win, max_members, res, -1, 0, 0, 0, 0};
     if (!res || !vq) {
         rc = -ENOMEM;
         goto out;
@@ -2324,6 +2333,14 @@ int bcp_pipeline_set_q_windowed(bcp_pipeline *pl, int on)
     if (!pl || (on != 0 && on != 1))
         return -EINVAL;
     pl->q_win = on;
+    return 0;
+}
+
+int bcp_pipeline_set_repair_windowed(bcp_pipeline *pl, int on)
+{
+    if (!pl || (on != 0 && on != 1))
+        return -EINVAL;
+    pl->repair_win = on;
     return 0;
 }
 

@@ -25,13 +25,16 @@
 //   REPAIR CHECK's prologue, pass and clean path; the mismatch path also
 //          corrects in place every bad byte whose member the stripe's mask
 //          allows -- P ^= Ps, Q ^= Qs, D_k ^= Ps -- and counts the bytes it
-//          fixed and the bytes it left (bcp_pq_repair_result).  No window
-//          form: a replayed byte is not tile-local.
+//          fixed and the bytes it left (bcp_pq_repair_result).
 //
-// The first three also exist over window replay (pq_win_desc, the _win entry
-// points): D_k is then the reference's replayed stream R_k of source k (bcp.h),
-// which the kernel reads by remapping, per source and tile, the offset it loads
-// from (pq_eff_off); outputs and bodies are addressed as before.
+// All four also exist over window replay (pq_win_desc, pq_repair_win_desc, the
+// _win entry points): D_k is then the reference's replayed stream R_k of source
+// k (bcp.h), which the kernel reads by remapping, per source and tile, the
+// offset it loads from (pq_eff_off); outputs and bodies are addressed as before.
+// A replayed byte is not tile-local, so windowed REPAIR writes a data byte only
+// from its home tile (where its source is not replayed) and the host launches
+// the tiles in phases, a source's echo tiles after its home tiles
+// (bcp_pq_repair_win_phases); a located byte of a replayed source is left.
 //
 // Schedule and load shape are the descriptor fold's (bcp_kernels.hip): a
 // device-wide atomicAdd-fed tile queue, wave-contiguous lanes, 16-byte
@@ -275,9 +278,13 @@ __device__ __forceinline__ uint32_t pq_fix_bytes(uint64_t at, uint32_t m, uint32
 // members are written.  pbody, qbody: the bodies at stripe offset 0.  A byte
 // that names position k at or past len_k (zero padding cannot be wrong), a
 // position the mask leaves out, or no position at all, is left.
-template <int U>
+// WIN: so is a position whose source is replayed at this tile (off >= lim_k,
+// wrun beside run): that byte's home is a tile of an earlier launch.  Where the
+// source is not replayed its effective offset is `off`, so the address and the
+// len test are the plain form's.
+template <int U, bool WIN>
 __device__ __forceinline__ void pq_repair_commit(bcp_pq_repair_result *rec, const v4u (&ps)[U], const v4u (&qs)[U],
-                                                 const_as<bcp_source> *run, uint32_t nsrc,
+                                                 const_as<bcp_source> *run, const_as<PqWin> *wrun, uint32_t nsrc,
                                                  unsigned long long allow, uint64_t pbody, uint64_t qbody,
                                                  uint64_t off, uint32_t lane_off) {
   uint32_t first = 0xFFFFFFFFu, np = 0, nq = 0, nboth = 0, nfound = 0, nfixed = 0, nleft = 0;
@@ -316,7 +323,8 @@ __device__ __forceinline__ void pq_repair_commit(bcp_pq_repair_result *rec, cons
 #pragma unroll 1
     for (uint32_t k = 0; k < nsrc; k++) {
       uint32_t hit = 0;
-      const bool may = (allow >> k) & 1ull;
+      bool may = (allow >> k) & 1ull;
+      if constexpr (WIN) may = may && off < wrun[k].lim;
       const uint64_t ptr = run[k].ptr, len = run[k].len;  // uniform; a (0, 0) source has no byte below len
 #pragma unroll
       for (int c = 0; c < 4; c++) {
@@ -433,7 +441,7 @@ __device__ __forceinline__ void pq_tile(const PqBatch &b, const PqWinTab &w, uin
     for (int u = 1; u < U; u++) any |= p[u] | q[u];
     if (__ballot((any[0] | any[1] | any[2] | any[3]) != 0u) == 0) return;  // clean: no store, no atomic
     if constexpr (F == kPqRepair)
-      pq_repair_commit<U>(res + tr->stripe, p, q, run, d->nsrc, d->allow, d->p, d->q, off, lane_off);
+      pq_repair_commit<U, WIN>(res + tr->stripe, p, q, run, wrun, d->nsrc, d->allow, d->p, d->q, off, lane_off);
     else pq_check_commit<U>(res + tr->stripe, p, q, d->nsrc, off, lane_off);
   } else if constexpr (SOLVE) {
 #pragma unroll
@@ -500,6 +508,13 @@ __global__ __launch_bounds__(kBlock) void pq_win_desc(PqBatchWin b, bcp_pq_check
   pq_body<U, (PqForm)F, true>(b.b, res, b.w);
 }
 
+// Windowed REPAIR (bcp_pq_repair_stripes_win_async): one launch per phase over
+// that phase's part of the tile and offw tables, in stream order.
+template <int U>
+__global__ __launch_bounds__(kBlock) void pq_repair_win_desc(PqBatchWin b, bcp_pq_repair_result *res) {
+  pq_body<U, kPqRepair, true>(b.b, res, b.w);
+}
+
 __global__ __launch_bounds__(kBlock) void pq_check_init(bcp_pq_check_result *res, uint32_t n) {
   const uint32_t i = blockIdx.x * kBlock + threadIdx.x;
   if (i < n) res[i] = bcp_pq_check_result{~0ull, 0ull, 0ull, 0ull};
@@ -561,6 +576,13 @@ hipError_t launch_pq_repair(hipStream_t st, int grid, int vecs, const PqBatch &b
   if (grid <= 0 || !pq_vecs_ok(vecs) || !res) return hipErrorInvalidValue;
   if (vecs == 8) hipLaunchKernelGGL((pq_repair_desc<8>), dim3(grid), dim3(kBlock), 0, st, b, res);
   else hipLaunchKernelGGL((pq_repair_desc<4>), dim3(grid), dim3(kBlock), 0, st, b, res);
+  return hipGetLastError();
+}
+
+hipError_t launch_pq_repair_win(hipStream_t st, int grid, int vecs, const PqBatchWin &b, bcp_pq_repair_result *res) {
+  if (grid <= 0 || !pq_vecs_ok(vecs) || !res) return hipErrorInvalidValue;
+  if (vecs == 8) hipLaunchKernelGGL((pq_repair_win_desc<8>), dim3(grid), dim3(kBlock), 0, st, b, res);
+  else hipLaunchKernelGGL((pq_repair_win_desc<4>), dim3(grid), dim3(kBlock), 0, st, b, res);
   return hipGetLastError();
 }
 

@@ -53,6 +53,33 @@ int bcp_pq_repair_verdict(const bcp_pq_check_result *r, uint32_t nsrc, int mode,
     return BCP_VERDICT_REPAIR;
 }
 
+/* The phase thresholds of a windowed repair (bcp.h): the distinct
+ * T_k = (lw_k + 1) * W below out_len of the non-empty members the mask admits,
+ * ascending.  At most nsrc of them, kept sorted by insertion. */
+int bcp_pq_repair_win_phases(const bcp_stripe *s, const bcp_source *run, uint64_t allow, uint64_t *bounds,
+                             uint32_t cap) {
+    if (!s || (s->nsrc && !run) || (cap && !bounds)) return -EINVAL;
+    if (s->nsrc > BCP_MAX_SOURCES || s->window % 32768u != 0) return -EINVAL;
+    const uint64_t W = s->window;
+    uint64_t e[BCP_MAX_SOURCES];
+    uint32_t m = 0;
+    for (uint32_t k = 0; W && k < s->nsrc; k++) {
+        const uint64_t len = run[k].len;
+        if (!(allow >> k & 1) || !len) continue;
+        const uint64_t lw = (len - 1) / W;
+        if (!s->out_len || lw >= (s->out_len - 1) / W) continue; /* T_k >= out_len (so T_k cannot wrap below) */
+        const uint64_t t = (lw + 1) * W;
+        uint32_t i = 0;
+        while (i < m && e[i] < t) i++;
+        if (i < m && e[i] == t) continue;
+        memmove(e + i + 1, e + i, (m - i) * sizeof(*e));
+        e[i] = t;
+        m++;
+    }
+    for (uint32_t i = 0; i < m && i < cap; i++) bounds[i] = e[i];
+    return (int)m + 1;
+}
+
 /* In-place patch of the blocks that differ (bcp.h): decisions 1-3 of
  * INTEGRATION.md, "Scrub repair". */
 #define PATCH_BLOCK 4096u

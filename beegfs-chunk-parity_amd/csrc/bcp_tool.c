@@ -43,8 +43,8 @@
  *       the exit status is then 1.  --q-windowed (with --also): items past the
  *       window have Q files too and are recovered like the others.
  *   bcp parity-verify [--db DIR] [--bad FILE] [--read PATH] [--q [--culprits FILE] [--q-windowed]
- *                     [--repair parity|all [--repair-members N] [--dry-run] [--repaired FILE]]]
- *                     <store_root> <ntargets>
+ *                     [--repair parity|all [--repair-members N] [--dry-run] [--repaired FILE]
+ *                     [--repair-windowed]]] <store_root> <ntargets>
  *       The scrub (no counterpart in the reference): for every item of the
  *       database (default <root>/st0/db) the batched pipeline reads the chunks
  *       and the parity body and compares them on the device
@@ -71,7 +71,10 @@
  *       summary line has the repair counts.  The first two lines and the lists
  *       describe the store as found; the exit status is 0 when every mismatch
  *       was repaired and nothing else is wrong (with --dry-run: as without
- *       --repair).
+ *       --repair).  --repair-windowed (with --repair and --q-windowed; without
+ *       either a usage error, exit 2): items past the window are repaired too
+ *       (bcp_pipeline_set_repair_windowed); without it they are reported and
+ *       left as they are.
  *
  * Items whose path would leave the store (absolute, "..") are skipped and
  * counted as refused; a run with refused items exits 1.
@@ -99,8 +102,8 @@ static int usage(void)
           "                          [--db DIR] [--corrupt FILE] [--also TARGET] [--lost FILE] [--q-windowed]\n"
           "                          <store_root> <ntargets> <target>\n"
           "       bcp parity-verify [--db DIR] [--bad FILE] [--read PATH] [--q [--culprits FILE] [--q-windowed]\n"
-          "                         [--repair parity|all [--repair-members N] [--dry-run] [--repaired FILE]]]\n"
-          "                         <store_root> <ntargets>\n"
+          "                         [--repair parity|all [--repair-members N] [--dry-run] [--repaired FILE]\n"
+          "                         [--repair-windowed]]] <store_root> <ntargets>\n"
           "       engine: --pipeline (default: batched pipeline on every GPU) | --protocol (per-rank\n"
           "               process_task, ranks as threads) | --procs (ranks as processes)\n"
           "       MODE (protocol P-role fold): pipelined (default) | batched\n"
@@ -113,7 +116,8 @@ static int usage(void)
           "            --culprits FILE (with --q only) lists path, data|p|q|many and the storage target\n"
           "            --repair parity|all (with --q only) corrects in place what the syndromes blame: P and Q files,\n"
           "            or chunks too; at most N files per item (default 1); --dry-run writes nothing; --repaired FILE\n"
-          "            lists path, data|p|q, target and bytes per file written\n"
+          "            lists path, data|p|q, target and bytes per file written; --repair-windowed (with --repair and\n"
+          "            --q-windowed only) also repairs items past the 10 MiB window, which are otherwise reported\n"
           "       --q-windowed (pipeline only): Q files for items past the 10 MiB window too; parity-gen (implies\n"
           "            --q; a --q run without it removes those Q files), parity-rebuild --also, parity-verify --q\n",
           stderr);
@@ -479,7 +483,7 @@ static int cmd_rebuild(int argc, char **argv)
 static int cmd_verify(int argc, char **argv)
 {
     const char *db = NULL, *bad = NULL, *culprits = NULL, *repaired = NULL;
-    int i = 0, with_q = 0, q_windowed = 0, repair = 0, dry_run = 0, bad_repair = 0;
+    int i = 0, with_q = 0, q_windowed = 0, repair = 0, dry_run = 0, bad_repair = 0, repair_windowed = 0;
     long members = 1;
     for (; i < argc && argv[i][0] == '-'; i++) {
         if (!strcmp(argv[i], "--db") && i + 1 < argc)
@@ -502,6 +506,8 @@ static int cmd_verify(int argc, char **argv)
             bad_repair |= *end || members < 1 || members > MAX_STORAGE_TARGETS + 2;
         } else if (!strcmp(argv[i], "--dry-run"))
             dry_run = 1;
+        else if (!strcmp(argv[i], "--repair-windowed"))
+            repair_windowed = 1;
         else if (!strcmp(argv[i], "--repaired") && i + 1 < argc)
             repaired = argv[++i];
         else if (!strcmp(argv[i], "--read") && i + 1 < argc) {
@@ -510,7 +516,8 @@ static int cmd_verify(int argc, char **argv)
         } else
             return usage();
     }
-    if (bad_repair || (repair && !with_q) || ((members != 1 || dry_run || repaired) && !repair)) {
+    if (bad_repair || (repair && !with_q) || ((members != 1 || dry_run || repaired) && !repair) ||
+        (repair_windowed && (!repair || !q_windowed))) {
         usage();
         return 2;
     }
@@ -547,6 +554,8 @@ static int cmd_verify(int argc, char **argv)
         rc = pipeline_on_all_gpus(&pl, 0);
         if (!rc && q_windowed)
             rc = bcp_pipeline_set_q_windowed(pl, 1);
+        if (!rc && repair_windowed)
+            rc = bcp_pipeline_set_repair_windowed(pl, 1);
         if (!rc && repair) {
             rc = bcp_pipeline_repair_q(pl, root, ntargets, items, n, repair, (uint32_t)members, dry_run, NULL, bad,
                                        culprits, repaired, stderr, &rs);

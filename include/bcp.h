@@ -55,7 +55,11 @@ extern "C" {
  * bcp_pq_stripes_win_async / bcp_pq_recover_stripes_win_async /
  * bcp_pq_check_stripes_win_async and the "last_desc_form" values 7, 8 and 9;
  * the scrub repair's bcp_pq_repair_stripes_async / bcp_pq_repair_result /
- * bcp_pq_repair_verdict / bcp_patch_file and the "last_desc_form" value 10.
+ * bcp_pq_repair_verdict / bcp_patch_file and the "last_desc_form" value 10;
+ * the repair over window replay, bcp_pq_repair_stripes_win_async /
+ * bcp_pq_repair_win_phases, the "last_desc_form" value 11, the read-only
+ * key "last_pq_repair_phases" and bcp_task.h's
+ * bcp_pipeline_set_repair_windowed.
  * 3 (r05): the pipeline's MAP read mode (BCP_READ_MAP), its
  * bcp_pipeline_timing fields and bcp_host_register_dma_src removed.
  * 2 (r04): bcp_task.h's bcp_run_stats gained `refused`, bcp_pipeline_opts
@@ -310,6 +314,50 @@ int bcp_pq_check_stripes_win_async(bcp_queue *q, const bcp_stripe *stripes, uint
                                    const bcp_source *sources, uint32_t nsources,
                                    const uint64_t *q_body, bcp_pq_check_result *results_dev);
 
+/* The repair over window replay.  One wrong byte of D_k in its last readable
+ * window shows at its home offset j and at every echo j + W, j + 2W, ... below
+ * out_len, each in another tile, so the tiles run in phases, one launch per
+ * phase in order on q:
+ *   thresholds  the distinct T_k = (lw_k + 1) * W over the positions k with
+ *               bit k in allow, len_k > 0 and T_k < out_len: E_1 < ... < E_m;
+ *   phase       of the tile at stripe offset off: #{i : E_i <= off}.  W is a
+ *               multiple of the largest tile, so no tile straddles a threshold;
+ *               a stripe with window 0, or without such a k, is all phase 0;
+ *   launches    1 + the largest phase of the batch.
+ * bcp_pq_repair_win_phases is that rule (pure host arithmetic, no device): for
+ * stripe s with its own source run (run[k] is position k; s->first_src is not
+ * used) it writes the first min(m, cap) thresholds, ascending, to bounds and
+ * returns m + 1, the number of phases.  -EINVAL for a null s, a null run with
+ * nsrc > 0, null bounds with cap > 0, a window that is neither 0 nor a multiple
+ * of 32768, and nsrc > BCP_MAX_SOURCES. */
+int bcp_pq_repair_win_phases(const bcp_stripe *s, const bcp_source *run, uint64_t allow, uint64_t *bounds,
+                             uint32_t cap);
+/* bcp_pq_repair_stripes_async over the replayed streams R_k.  Signature and
+ * validation are its own, except that stripes[s].window may be 0 or a non-zero
+ * multiple of 32768 and a batch may mix them; a batch without any window is
+ * the namesake's launch.  The rules are the namesake's with Ps and Qs over the
+ * R_k and one more clause: a byte that names position k is written, as
+ * D_k[j] ^= Ps, only by a tile at which source k is not replayed (off <
+ * T_k, where R_k[j] is D_k'[j] itself, so j < len_k is the same test); at a
+ * tile where k is replayed the byte is left.  P and Q are addressed with the
+ * stream offset.  A byte of D_k is thus written only by its home tile and read
+ * again only by k's echo tiles, which lie in a later phase: the result does
+ * not depend on timing.  A member the mask leaves out is never written.
+ * The record is the state as found by each phase: a corrected data byte counts
+ * once, at its home -- its echoes are clean by the time their phase runs -- so
+ * p_bad and q_bad are at most bcp_pq_check_stripes_win_async's for the same
+ * stripe, and equal when nothing corrected had an echo; first_bad and members
+ * equal the check's whenever every stream offset has at most one wrong member;
+ * fixed + left is the number of bad bytes the phases saw.  For a data member
+ * outside the mask every echo counts in p_bad, q_bad and left, as the check
+ * counts them.  The namesake's limit holds: two members wrong at one stream
+ * offset can name a third, and the record's members may then differ from a
+ * check's made before.  Across the whole batch no two members may overlap.
+ * Nothing is written at or past len_k or out_len. */
+int bcp_pq_repair_stripes_win_async(bcp_queue *q, const bcp_stripe *stripes, uint32_t nstripes,
+                                    const bcp_source *sources, uint32_t nsources, const uint64_t *q_body,
+                                    const uint64_t *allow, bcp_pq_repair_result *results_dev);
+
 /* Which single member a record blames (pure host arithmetic, no device,
  * bcp_pq_host.c).  Returns the kind, or -EINVAL for a null record;
  * *position (may be null) is the data position for DATA, else -1. */
@@ -472,7 +520,11 @@ int bcp_set_option(bcp_engine *eng, const char *key, int value);
  * form, bcp_pq_check_stripes_async, 7 / 8 / 9 = the windowed kernels of
  * bcp_pq_stripes_win_async / bcp_pq_recover_stripes_win_async /
  * bcp_pq_check_stripes_win_async, taken by a batch with a windowed stripe,
- * 10 = the repair form, bcp_pq_repair_stripes_async). */
+ * 10 = the repair form, bcp_pq_repair_stripes_async, 11 = its windowed
+ * kernel, taken by a bcp_pq_repair_stripes_win_async batch with a windowed
+ * stripe), and "last_pq_repair_phases": the launches the latest
+ * bcp_pq_repair_stripes_win_async call made (1 for a batch without a window,
+ * 0 for one without a tile). */
 int bcp_get_option(bcp_engine *eng, const char *key, int *value);
 /* Timer slots for bcp_queue_mark / bcp_queue_elapsed_ms. */
 #define BCP_TIMER_SLOTS 64

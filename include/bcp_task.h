@@ -735,7 +735,8 @@ int bcp_pipeline_verify_q(bcp_pipeline *pl, const char *store_root, int ntargets
 #define BCP_REPAIRED_DONE      1  /* corrected, checked and written */
 #define BCP_REPAIRED_DRY       2  /* dry_run: corrected on the device and checked clean, nothing written */
 #define BCP_REPAIRED_POLICY    3  /* refused by the policy */
-#define BCP_REPAIRED_UNLOCATED 4  /* BAD_NOWHERE, bytes left uncorrected, q_state not CHECKED, or windowed */
+#define BCP_REPAIRED_UNLOCATED 4  /* BAD_NOWHERE, bytes left uncorrected, q_state not CHECKED, or windowed
+                                     (without bcp_pipeline_set_repair_windowed) */
 #define BCP_REPAIRED_CHANGED   5  /* a file's size or mtime is not what the batch's stat saw: nothing written */
 #define BCP_REPAIRED_FAILED    6  /* the second check was not clean, or a write failed; counts in errors */
 typedef struct {
@@ -794,6 +795,18 @@ int bcp_pipeline_set_q_parity(bcp_pipeline *pl, int on);
  * Q on and this switch off unlinks the Q files of windowed items, as it
  * always has: turn it on for every run over a store that uses it. */
 int bcp_pipeline_set_q_windowed(bcp_pipeline *pl, int on);
+/* Repair of windowed items (0 or 1, anything else -EINVAL; default 0:
+ * bcp_pipeline_repair_q gives them UNLOCATED, as without this call).  With it
+ * on, a CHECKED windowed MISMATCH item (which needs bcp_pipeline_set_q_windowed)
+ * goes through the policy like any other; its stripe carries BCP_WINDOW_BYTES
+ * and the batch's repair and second check are
+ * bcp_pq_repair_stripes_win_async and bcp_pq_check_stripes_win_async (bcp.h:
+ * the phases, and what the record counts).  Policy, the left -> UNLOCATED
+ * rule, the members comparison, the clean second check, the write-back, dry
+ * run and the lists are unchanged; repair_launches still counts one per batch
+ * stage, bytes_fixed is the record's `fixed` -- a corrected chunk byte counts
+ * once, however often the streams replay it. */
+int bcp_pipeline_set_repair_windowed(bcp_pipeline *pl, int on);
 /* Of the last run: Q files written, items left without one for lack of a Q
  * target, and windowed items.  Each pointer may be NULL. */
 int bcp_pipeline_q_stats(const bcp_pipeline *pl, uint64_t *written, uint64_t *no_target, uint64_t *windowed);
