@@ -226,6 +226,10 @@ _SIGS = {
                                           ctypes.c_uint32, ctypes.POINTER(PqLost)], ctypes.c_int),
     "bcp_pq_check_stripes_win_async": ([_V, ctypes.POINTER(Stripe), ctypes.c_uint32, ctypes.POINTER(Source),
                                         ctypes.c_uint32, ctypes.POINTER(ctypes.c_uint64), _V], ctypes.c_int),
+    "bcp_pq_rebuild_check_stripes_async": ([_V, ctypes.POINTER(Stripe), ctypes.c_uint32, ctypes.POINTER(Source),
+                                            ctypes.c_uint32, ctypes.POINTER(PqLost), _V], ctypes.c_int),
+    "bcp_pq_rebuild_check_stripes_win_async": ([_V, ctypes.POINTER(Stripe), ctypes.c_uint32, ctypes.POINTER(Source),
+                                                ctypes.c_uint32, ctypes.POINTER(PqLost), _V], ctypes.c_int),
     "bcp_pq_culprit": ([ctypes.POINTER(PqCheckResult), ctypes.POINTER(ctypes.c_int)], ctypes.c_int),
     "bcp_pq_repair_stripes_async": ([_V, ctypes.POINTER(Stripe), ctypes.c_uint32, ctypes.POINTER(Source),
                                      ctypes.c_uint32, ctypes.POINTER(ctypes.c_uint64),
@@ -618,6 +622,16 @@ class Queue:
         lo = (PqLost * max(len(lost), 1))(*[x if isinstance(x, PqLost) else PqLost(*x) for x in lost])
         call("bcp_pq_recover_stripes_win_async" if windowed else "bcp_pq_recover_stripes_async", self.h, st,
              len(stripes), so, len(sources), lo)
+
+    def pq_rebuild_check(self, stripes, sources, lost, results_ptr: int, windowed=False):
+        """Verified rebuild: pq_recover's arguments for the case it refuses -- P and Q present, exactly x
+        lost (y = PQ_NONE).  Member x is written as the XOR of the survivors and P; results_ptr: device
+        memory for len(stripes) CheckResult records, where Q does not agree with the bytes written."""
+        st = (Stripe * max(len(stripes), 1))(*[Stripe(*s) for s in stripes])
+        so = (Source * max(len(sources), 1))(*[Source(*s) for s in sources])
+        lo = (PqLost * max(len(lost), 1))(*[x if isinstance(x, PqLost) else PqLost(*x) for x in lost])
+        call("bcp_pq_rebuild_check_stripes_win_async" if windowed else "bcp_pq_rebuild_check_stripes_async", self.h,
+             st, len(stripes), so, len(sources), lo, _V(results_ptr))
 
     def pq_check(self, stripes, sources, q_body, results_ptr: int, windowed=False):
         """Syndromes of every stripe: stripes as in pq_stripes but dst = P body and q_body[s] = Q body

@@ -42,7 +42,7 @@ struct bcp_engine {
   pthread_mutex_t lock = PTHREAD_MUTEX_INITIALIZER;
   std::atomic<int> last_stream_vecs{0};  // U of the latest xor_stream launch (tools)
   std::atomic<int> last_desc_vecs{0};    // U of the latest descriptor-kernel launch (tools)
-  std::atomic<int> last_desc_form{0};    // 1 xor_desc (desc_tiles), 2 xor_desc_args, 3 check_desc, 4 / 5 / 6 pq_desc gen / solve / check, 7 / 8 / 9 their windowed forms, 10 pq_repair_desc, 11 pq_repair_win_desc
+  std::atomic<int> last_desc_form{0};    // 1 xor_desc (desc_tiles), 2 xor_desc_args, 3 check_desc, 4 / 5 / 6 pq_desc gen / solve / check, 7 / 8 / 9 their windowed forms, 10 pq_repair_desc, 11 pq_repair_win_desc, 12 pq_rebuild_desc, 13 pq_rebuild_win_desc
   std::atomic<int> last_pq_repair_phases{0};  // launches of the latest bcp_pq_repair_stripes_win_async
 };
 
@@ -1230,7 +1230,9 @@ const Gf256 g_gf;
 // REPAIR form: CHECK's batch and validation, its own records, the stripes'
 // masks in their table records; with `win` and a windowed stripe its tiles are
 // ordered by (phase, stripe, subtile) and each phase is a launch of its own
-// (bcp_pq_repair_win_phases is the rule).
+// (bcp_pq_repair_win_phases is the rule).  `rebuild` with `lost` is the
+// VERIFY-REBUILD form: SOLVE's batch, validation and cover with P present and
+// exactly one member lost, bcp_check_result records initialised on the queue.
 // The staged tables are the stripes' records, their source runs copied in the
 // caller's order, and one record per tile; they go through stage_tables with
 // the pointer-table threshold, since the kernel reads them once per tile.
@@ -1241,7 +1243,7 @@ const Gf256 g_gf;
 static int submit_pq(bcp_queue *q, const bcp_stripe *stripes, uint32_t nstripes, const bcp_source *sources,
                      uint32_t nsources, const uint64_t *q_dst, const bcp_pq_lost *lost,
                      bcp_pq_check_result *check = nullptr, bool win = false, const uint64_t *allow = nullptr,
-                     bcp_pq_repair_result *repair = nullptr) {
+                     bcp_pq_repair_result *repair = nullptr, bcp_check_result *rebuild = nullptr) {
   bcp_engine *e = q->eng;
   uint64_t tiles8 = 0, nstaged = 0;
   bool windowed = false;
@@ -1260,7 +1262,11 @@ static int submit_pq(bcp_queue *q, const bcp_stripe *stripes, uint32_t nstripes,
       const bcp_pq_lost &l = lost[i];
       const bool two = l.y != BCP_PQ_NONE;
       if (l.x >= s.nsrc || (two && (l.y <= l.x || l.y >= s.nsrc))) return -EINVAL;
-      if ((l.p != 0) != two) return -EINVAL;  // P present with one loss is RAID-5; P lost leaves Q for one member
+      if (rebuild) {
+        if (two || !l.p || !l.q) return -EINVAL;  // VERIFY-REBUILD: exactly x lost, P and Q both present
+      } else if ((l.p != 0) != two) {
+        return -EINVAL;  // P present with one loss is RAID-5; P lost leaves Q for one member
+      }
       if (s.out_len && !l.q) return -EINVAL;
       if (sources[s.first_src + l.x].len != 0 || (two && sources[s.first_src + l.y].len != 0)) return -EINVAL;
       if (l.len_x > s.out_len || (two && l.len_y > s.out_len)) return -EINVAL;
@@ -1283,6 +1289,11 @@ static int submit_pq(bcp_queue *q, const bcp_stripe *stripes, uint32_t nstripes,
     (void)hipGetLastError();
     HIP_RC(launch_pq_repair_init(q->stream, repair, nstripes));
     if (win) e->last_pq_repair_phases.store(0, std::memory_order_relaxed);
+  }
+  if (rebuild) {
+    if (q->broken) return -EIO;
+    (void)hipGetLastError();
+    HIP_RC(launch_check_init(q->stream, rebuild, nstripes));
   }
   if (tiles8 == 0) return 0;
   int vecs = e->tuning.desc_vecs;
@@ -1343,7 +1354,10 @@ static int submit_pq(bcp_queue *q, const bcp_stripe *stripes, uint32_t nstripes,
         r.len_x = l.len_x;
         r.dy = two ? l.dst_y : 0;
         r.len_y = two ? l.len_y : 0;
-        if (two) {
+        if (rebuild) {
+          r.ca = g_gf.pow((int)l.x);  // the residual Qs ^ g^x * Ps
+          r.cb = 0;
+        } else if (two) {
           // D_x = A * Ps ^ B * Qs with d = g^(y-x) ^ 1, A = g^(y-x) / d, B = g^(-x) / d
           const uint8_t gyx = g_gf.pow((int)(l.y - l.x)), dd = (uint8_t)(gyx ^ 1);
           r.ca = g_gf.div(gyx, dd);
@@ -1457,12 +1471,15 @@ static int submit_pq(bcp_queue *q, const bcp_stripe *stripes, uint32_t nstripes,
   }
   const int form = check ? 2 : lost ? 1 : 0;
   const hipError_t le = repair     ? launch_pq_repair(q->stream, grid, vecs, b, repair)
+                        : rebuild  ? (windowed ? launch_pq_rebuild_win(q->stream, grid, vecs, bw, rebuild)
+                                               : launch_pq_rebuild(q->stream, grid, vecs, b, rebuild))
                         : windowed ? launch_pq_win(q->stream, grid, vecs, form, bw, check)
                         : check    ? launch_pq_check(q->stream, grid, vecs, b, check)
                                    : launch_pq(q->stream, grid, vecs, lost != nullptr, b);
   if (le == hipSuccess) {
     e->last_desc_vecs.store(vecs, std::memory_order_relaxed);
-    e->last_desc_form.store(repair ? 10 : (windowed ? 7 : 4) + form, std::memory_order_relaxed);
+    e->last_desc_form.store(repair ? 10 : rebuild ? (windowed ? 13 : 12) : (windowed ? 7 : 4) + form,
+                            std::memory_order_relaxed);
     if (repair && win) e->last_pq_repair_phases.store(1, std::memory_order_relaxed);
   }
   if ((rc = queue_launched(q, le, (uint64_t)ntiles + (uint64_t)grid))) return rc;
@@ -1509,6 +1526,19 @@ extern "C" int bcp_pq_repair_stripes_async(bcp_queue *q, const bcp_stripe *strip
   return submit_pq(q, stripes, nstripes, sources, nsources, q_body, nullptr, nullptr, false, allow, results_dev);
 }
 
+// The VERIFY-REBUILD form (bcp.h): SOLVE's batch with P present and one member lost, the records
+// bcp_check_result.
+extern "C" int bcp_pq_rebuild_check_stripes_async(bcp_queue *q, const bcp_stripe *stripes, uint32_t nstripes,
+                                                  const bcp_source *sources, uint32_t nsources,
+                                                  const bcp_pq_lost *lost, bcp_check_result *results_dev) {
+  if (!q || !stripes || !lost || !results_dev || (nsources && !sources)) return -EINVAL;
+  if (!nstripes) return 0;
+  int rc = set_device(q->eng);
+  if (rc) return rc;
+  return submit_pq(q, stripes, nstripes, sources, nsources, nullptr, lost, nullptr, false, nullptr, nullptr,
+                   results_dev);
+}
+
 // The first three over window replay (bcp.h): a stripe's window may be 0 or a
 // multiple of the largest tile.
 extern "C" int bcp_pq_stripes_win_async(bcp_queue *q, const bcp_stripe *stripes, uint32_t nstripes,
@@ -1550,6 +1580,17 @@ extern "C" int bcp_pq_repair_stripes_win_async(bcp_queue *q, const bcp_stripe *s
   int rc = set_device(q->eng);
   if (rc) return rc;
   return submit_pq(q, stripes, nstripes, sources, nsources, q_body, nullptr, nullptr, true, allow, results_dev);
+}
+
+extern "C" int bcp_pq_rebuild_check_stripes_win_async(bcp_queue *q, const bcp_stripe *stripes, uint32_t nstripes,
+                                                      const bcp_source *sources, uint32_t nsources,
+                                                      const bcp_pq_lost *lost, bcp_check_result *results_dev) {
+  if (!q || !stripes || !lost || !results_dev || (nsources && !sources)) return -EINVAL;
+  if (!nstripes) return 0;
+  int rc = set_device(q->eng);
+  if (rc) return rc;
+  return submit_pq(q, stripes, nstripes, sources, nsources, nullptr, lost, nullptr, true, nullptr, nullptr,
+                   results_dev);
 }
 
 extern "C" int bcp_xor_strided_async(bcp_queue *q, void *dst, uint64_t dst_stride, const void *src,

@@ -278,8 +278,8 @@ struct RingArgs {
 
 // ---------------------------------------------------------------------------
 // P + Q parity (bcp_pq.hip; bcp_pq_stripes_async, bcp_pq_recover_stripes_async,
-// bcp_pq_check_stripes_async, bcp_pq_repair_stripes_async, and the first
-// three's _win namesakes further down).
+// bcp_pq_check_stripes_async, bcp_pq_repair_stripes_async,
+// bcp_pq_rebuild_check_stripes_async, and their _win namesakes further down).
 // One record per stripe and one per tile, both written by the host: the
 // sources of a run stay in the caller's position order (source k has
 // coefficient g^k), so nothing here is sorted.
@@ -288,9 +288,9 @@ struct alignas(16) PqStripe {
     uint64_t p, q;          // GEN: P / Q output (p 0: no P); SOLVE: P / Q body (p 0: P is lost); CHECK, REPAIR: P / Q body
     uint64_t out_len;       // GEN: bytes of each output; SOLVE, CHECK, REPAIR: readable bytes of p and q
     uint32_t first_src, nsrc;
-    uint64_t dx, len_x;     // SOLVE: member x, its first len_x bytes
+    uint64_t dx, len_x;     // SOLVE, REBUILD: member x, its first len_x bytes
     uint64_t dy, len_y;     // SOLVE: member y (len_y 0: not asked for)
-    uint32_t ca, cb;        // SOLVE: D_x = ca * Ps ^ cb * Qs over GF(2^8)
+    uint32_t ca, cb;        // SOLVE: D_x = ca * Ps ^ cb * Qs over GF(2^8); REBUILD: ca = g^x (residual Qs ^ ca * Ps), cb unused
     uint64_t allow;         // REPAIR: the members that may be written, bit layout of bcp_pq_check_result.members
 };
 static_assert(sizeof(PqStripe) == 80, "five 16-byte scalar loads");
@@ -319,6 +319,10 @@ hipError_t launch_pq_check(hipStream_t st, int grid, int vecs, const PqBatch &b,
 // launch_pq_repair_init sets n records to {UINT64_MAX, 0, 0, 0, 0, 0}.
 hipError_t launch_pq_repair_init(hipStream_t st, bcp_pq_repair_result *res, uint32_t n);
 hipError_t launch_pq_repair(hipStream_t st, int grid, int vecs, const PqBatch &b, bcp_pq_repair_result *res);
+// VERIFY-REBUILD form (bcp_pq_rebuild_check_stripes_async): SOLVE's batch with P
+// present and one member lost; member x is stored and res[s] says where Q does
+// not agree with it.  The records are bcp_check_result: launch_check_init.
+hipError_t launch_pq_rebuild(hipStream_t st, int grid, int vecs, const PqBatch &b, bcp_check_result *res);
 
 // The windowed forms (bcp_pq_*_win_async): a batch in which some stripe has a
 // window W (a multiple of kPqWindowUnit, so a tile lies in one window and the
@@ -345,6 +349,8 @@ hipError_t launch_pq_win(hipStream_t st, int grid, int vecs, int form, const PqB
 // tiles and offw pointing at that phase's part of the tables, which the host
 // orders by (phase, stripe, subtile); accounting as launch_pq per launch.
 hipError_t launch_pq_repair_win(hipStream_t st, int grid, int vecs, const PqBatchWin &b, bcp_pq_repair_result *res);
+// Windowed VERIFY-REBUILD (bcp_pq_rebuild_check_stripes_win_async): nothing is written in place, one launch.
+hipError_t launch_pq_rebuild_win(hipStream_t st, int grid, int vecs, const PqBatchWin &b, bcp_check_result *res);
 
 // Kernel launchers (bcp_kernels.hip).  All return hipError_t.
 // Streaming fold.  Consumes ceil(ntiles / grab) + grid counts of a.ctr; the

@@ -8,7 +8,7 @@
 // four packed bytes of a dword at a time (mul2): no multiply, no table, no
 // LDS.  One pass over the sources yields both.
 //
-// Four forms of that pass:
+// Five forms of that pass:
 //   GEN    the epilogue stores Q, and P when the stripe has a P address;
 //   SOLVE  the sources are the survivors (lost positions have len 0 and
 //          contribute 2*q steps only), the P and Q bodies are loaded with the
@@ -26,9 +26,15 @@
 //          corrects in place every bad byte whose member the stripe's mask
 //          allows -- P ^= Ps, Q ^= Qs, D_k ^= Ps -- and counts the bytes it
 //          fixed and the bytes it left (bcp_pq_repair_result).
+//   VERIFY-REBUILD  SOLVE's prologue and pass with P present and exactly one
+//          member x lost (the case SOLVE leaves to the XOR kernel): Ps is D_x
+//          and is stored, cut to len_x; the residual Qs ^ g^x * Ps, zero where
+//          the survivors, P and Q agree, is judged like CHECK's syndromes --
+//          one ballot for a clean tile, else first offset and count to the
+//          stripe's record (bcp_check_result).  Nothing is located or altered.
 //
-// All four also exist over window replay (pq_win_desc, pq_repair_win_desc, the
-// _win entry points): D_k is then the reference's replayed stream R_k of source
+// All five also exist over window replay (pq_win_desc, pq_repair_win_desc,
+// pq_rebuild_win_desc, the _win entry points): D_k is then the reference's replayed stream R_k of source
 // k (bcp.h), which the kernel reads by remapping, per source and tile, the
 // offset it loads from (pq_eff_off); outputs and bodies are addressed as before.
 // A replayed byte is not tile-local, so windowed REPAIR writes a data byte only
@@ -362,7 +368,39 @@ __device__ __forceinline__ void pq_repair_commit(bcp_pq_repair_result *rec, cons
   }
 }
 
-enum PqForm { kPqGen = 0, kPqSolve = 1, kPqCheck = 2, kPqRepair = 3 };
+// ---- VERIFY-REBUILD form: where Q does not agree with the rebuilt member ----
+// Mismatch path, every lane of the wave: r = Qs ^ g^x * Ps of this lane's
+// vectors, already cut to len_x.  The smallest bad offset and the number of bad
+// bytes, reduced over the wave, one fetch_min and one fetch_add on the record.
+template <int U>
+__device__ __forceinline__ void pq_rebuild_commit(bcp_check_result *rec, const v4u (&r)[U], uint64_t off,
+                                                  uint32_t lane_off) {
+  uint32_t first = 0xFFFFFFFFu, nbad = 0;
+#pragma unroll
+  for (int u = 0; u < U; u++) {
+#pragma unroll
+    for (int c = 0; c < 4; c++) {
+      const uint32_t h = nz_bytes(r[u][c]);
+      nbad += (uint32_t)__builtin_popcount(h);
+      if (h) {
+        const uint32_t o = lane_off + (uint32_t)u * 1024u + (uint32_t)c * 4u + ((uint32_t)__builtin_ctz(h) >> 3);
+        first = o < first ? o : first;
+      }
+    }
+  }
+  unsigned long long f = first == 0xFFFFFFFFu ? ~0ull : off + first, cnt = nbad;
+  for (int o = 32; o > 0; o >>= 1) {
+    const unsigned long long fo = __shfl_xor(f, o, 64);
+    f = fo < f ? fo : f;
+    cnt += __shfl_xor(cnt, o, 64);
+  }
+  if ((threadIdx.x & 63u) == 0 && cnt) {
+    __hip_atomic_fetch_min((unsigned long long *)&rec->first_bad, f, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    __hip_atomic_fetch_add((unsigned long long *)&rec->bad_bytes, cnt, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  }
+}
+
+enum PqForm { kPqGen = 0, kPqSolve = 1, kPqCheck = 2, kPqRepair = 3, kPqRebuild = 4 };
 
 // WIN: the windowed instantiations (PqBatchWin's two more tables, w); a stripe
 // without a window in such a batch has lim = UINT64_MAX on every source and
@@ -443,6 +481,18 @@ __device__ __forceinline__ void pq_tile(const PqBatch &b, const PqWinTab &w, uin
     if constexpr (F == kPqRepair)
       pq_repair_commit<U, WIN>(res + tr->stripe, p, q, run, wrun, d->nsrc, d->allow, d->p, d->q, off, lane_off);
     else pq_check_commit<U>(res + tr->stripe, p, q, d->nsrc, off, lane_off);
+  } else if constexpr (F == kPqRebuild) {
+#pragma unroll
+    for (int u = 0; u < U; u++) q[u] ^= qb[u];  // p = Ps = D_x, q = Qs
+    const uint64_t left = d->len_x - off;       // > 0: the tiles cover [0, len_x) only
+    mulc_acc<U>(q, p, d->ca);                   // q = r = Qs ^ g^x * Ps
+    pq_store<U>(d->dx + off, left, T, lane_off, p);
+    if (left < T) pq_mask_tail<U>(q, (uint32_t)left, lane_off);  // the stripe's last covered tile (uniform)
+    v4u any = q[0];
+#pragma unroll
+    for (int u = 1; u < U; u++) any |= q[u];
+    if (__ballot((any[0] | any[1] | any[2] | any[3]) != 0u) == 0) return;  // clean: no further store, no atomic
+    pq_rebuild_commit<U>(res + tr->stripe, q, off, lane_off);
   } else if constexpr (SOLVE) {
 #pragma unroll
     for (int u = 0; u < U; u++) q[u] ^= qb[u];  // p = Ps, q = Qs
@@ -515,6 +565,20 @@ __global__ __launch_bounds__(kBlock) void pq_repair_win_desc(PqBatchWin b, bcp_p
   pq_body<U, kPqRepair, true>(b.b, res, b.w);
 }
 
+// The VERIFY-REBUILD form (bcp_pq_rebuild_check_stripes_async and its _win
+// namesake): SOLVE's batch with P present, one bcp_check_result per stripe
+// (initialised by check_init before the launch).  Nothing is written in place,
+// so the windowed one needs no phases.
+template <int U>
+__global__ __launch_bounds__(kBlock) void pq_rebuild_desc(PqBatch b, bcp_check_result *res) {
+  pq_body<U, kPqRebuild>(b, res);
+}
+
+template <int U>
+__global__ __launch_bounds__(kBlock) void pq_rebuild_win_desc(PqBatchWin b, bcp_check_result *res) {
+  pq_body<U, kPqRebuild, true>(b.b, res, b.w);
+}
+
 __global__ __launch_bounds__(kBlock) void pq_check_init(bcp_pq_check_result *res, uint32_t n) {
   const uint32_t i = blockIdx.x * kBlock + threadIdx.x;
   if (i < n) res[i] = bcp_pq_check_result{~0ull, 0ull, 0ull, 0ull};
@@ -583,6 +647,20 @@ hipError_t launch_pq_repair_win(hipStream_t st, int grid, int vecs, const PqBatc
   if (grid <= 0 || !pq_vecs_ok(vecs) || !res) return hipErrorInvalidValue;
   if (vecs == 8) hipLaunchKernelGGL((pq_repair_win_desc<8>), dim3(grid), dim3(kBlock), 0, st, b, res);
   else hipLaunchKernelGGL((pq_repair_win_desc<4>), dim3(grid), dim3(kBlock), 0, st, b, res);
+  return hipGetLastError();
+}
+
+hipError_t launch_pq_rebuild(hipStream_t st, int grid, int vecs, const PqBatch &b, bcp_check_result *res) {
+  if (grid <= 0 || !pq_vecs_ok(vecs) || !res) return hipErrorInvalidValue;
+  if (vecs == 8) hipLaunchKernelGGL((pq_rebuild_desc<8>), dim3(grid), dim3(kBlock), 0, st, b, res);
+  else hipLaunchKernelGGL((pq_rebuild_desc<4>), dim3(grid), dim3(kBlock), 0, st, b, res);
+  return hipGetLastError();
+}
+
+hipError_t launch_pq_rebuild_win(hipStream_t st, int grid, int vecs, const PqBatchWin &b, bcp_check_result *res) {
+  if (grid <= 0 || !pq_vecs_ok(vecs) || !res) return hipErrorInvalidValue;
+  if (vecs == 8) hipLaunchKernelGGL((pq_rebuild_win_desc<8>), dim3(grid), dim3(kBlock), 0, st, b, res);
+  else hipLaunchKernelGGL((pq_rebuild_win_desc<4>), dim3(grid), dim3(kBlock), 0, st, b, res);
   return hipGetLastError();
 }
 

@@ -59,7 +59,9 @@ extern "C" {
  * the repair over window replay, bcp_pq_repair_stripes_win_async /
  * bcp_pq_repair_win_phases, the "last_desc_form" value 11, the read-only
  * key "last_pq_repair_phases" and bcp_task.h's
- * bcp_pipeline_set_repair_windowed.
+ * bcp_pipeline_set_repair_windowed; the verified rebuild's
+ * bcp_pq_rebuild_check_stripes_async / bcp_pq_rebuild_check_stripes_win_async,
+ * and the "last_desc_form" values 12 and 13.
  * 3 (r05): the pipeline's MAP read mode (BCP_READ_MAP), its
  * bcp_pipeline_timing fields and bcp_host_register_dma_src removed.
  * 2 (r04): bcp_task.h's bcp_run_stats gained `refused`, bcp_pipeline_opts
@@ -228,6 +230,28 @@ typedef struct bcp_pq_lost {
  * position whose source has len != 0 and for len_x or len_y above out_len. */
 int bcp_pq_recover_stripes_async(bcp_queue *q, const bcp_stripe *stripes, uint32_t nstripes,
                                  const bcp_source *sources, uint32_t nsources, const bcp_pq_lost *lost);
+/* Verified rebuild: the one combination the call above refuses.  Exactly one
+ * data member x is lost and P and Q both survive, so P alone gives the member
+ * and Q, otherwise idle, vouches for it.  With Ps = P ^ XOR_{k != x} D_k and
+ * Qs = Q ^ XOR_{k != x} g^k * D_k over the survivors:
+ *   dst_x[j] = Ps[j]                            0 <= j < len_x
+ *   byte j < len_x is bad when Qs[j] != g^x * Ps[j]
+ * lost[s]: p and q required (out_len readable bytes each, only read), x lost
+ * (its source has len 0), y = BCP_PQ_NONE; len_x <= out_len, dst_x required
+ * when len_x > 0; anything else -EINVAL, as is a window.  The bytes written
+ * are what bcp_xor_stripes_async writes over the survivors and P, whatever the
+ * record says: the call reports, it does not alter.  results_dev: nstripes
+ * bcp_check_result records in device memory, fully written by this call's work
+ * for every stripe -- {UINT64_MAX, 0} for a clean one, also for len_x == 0 and
+ * for batches with no tile at all; first_bad is the smallest bad j, bad_bytes
+ * their number, both exact.  A fault confined to one member at offset j < len_x
+ * -- a survivor, P or Q -- always makes j bad (g has order 255); it cannot be
+ * located while x is missing.  Only [0, len_x) is read and judged: nothing is
+ * read outside [body, body+out_len) or a source's len, nothing is written
+ * outside [dst_x, dst_x+len_x) and the records. */
+int bcp_pq_rebuild_check_stripes_async(bcp_queue *q, const bcp_stripe *stripes, uint32_t nstripes,
+                                       const bcp_source *sources, uint32_t nsources, const bcp_pq_lost *lost,
+                                       bcp_check_result *results_dev);
 
 /* One record per stripe of a syndrome check (bcp_pq_check_stripes_async).
  * With Ps = P ^ XOR_k D_k and Qs = Q ^ XOR_k g^k * D_k, a byte j is bad when
@@ -313,6 +337,12 @@ int bcp_pq_recover_stripes_win_async(bcp_queue *q, const bcp_stripe *stripes, ui
 int bcp_pq_check_stripes_win_async(bcp_queue *q, const bcp_stripe *stripes, uint32_t nstripes,
                                    const bcp_source *sources, uint32_t nsources,
                                    const uint64_t *q_body, bcp_pq_check_result *results_dev);
+/* bcp_pq_rebuild_check_stripes_async with Ps and Qs over the survivors'
+ * replayed streams: dst_x = R_x cut to len_x, which is D_x; an offset below
+ * len_x that a survivor's wrong byte is replayed to counts like its home. */
+int bcp_pq_rebuild_check_stripes_win_async(bcp_queue *q, const bcp_stripe *stripes, uint32_t nstripes,
+                                           const bcp_source *sources, uint32_t nsources, const bcp_pq_lost *lost,
+                                           bcp_check_result *results_dev);
 
 /* The repair over window replay.  One wrong byte of D_k in its last readable
  * window shows at its home offset j and at every echo j + W, j + 2W, ... below
@@ -522,7 +552,10 @@ int bcp_set_option(bcp_engine *eng, const char *key, int value);
  * bcp_pq_check_stripes_win_async, taken by a batch with a windowed stripe,
  * 10 = the repair form, bcp_pq_repair_stripes_async, 11 = its windowed
  * kernel, taken by a bcp_pq_repair_stripes_win_async batch with a windowed
- * stripe), and "last_pq_repair_phases": the launches the latest
+ * stripe, 12 = the verified-rebuild form,
+ * bcp_pq_rebuild_check_stripes_async, 13 = its windowed kernel, taken by a
+ * bcp_pq_rebuild_check_stripes_win_async batch with a windowed stripe), and
+ * "last_pq_repair_phases": the launches the latest
  * bcp_pq_repair_stripes_win_async call made (1 for a batch without a window,
  * 0 for one without a tile). */
 int bcp_get_option(bcp_engine *eng, const char *key, int *value);
