@@ -65,6 +65,7 @@ class PqRepairResult(ctypes.Structure):
 
 PQ_REPAIR_CLEAN = PQ_CHECK_CLEAN + (0, 0)
 REPAIR_PARITY, REPAIR_ALL = 1, 2  # the policy's mode: only P and Q files are written / chunks too
+PQ_KEEP_P, PQ_KEEP_Q = 1, 2  # bcp_restore_plan's keep
 VERDICT_CLEAN, VERDICT_REPAIR, VERDICT_UNLOCATED, VERDICT_POLICY = range(4)  # bcp_pq_repair_verdict
 
 
@@ -230,6 +231,9 @@ _SIGS = {
                                             ctypes.c_uint32, ctypes.POINTER(PqLost), _V], ctypes.c_int),
     "bcp_pq_rebuild_check_stripes_win_async": ([_V, ctypes.POINTER(Stripe), ctypes.c_uint32, ctypes.POINTER(Source),
                                                 ctypes.c_uint32, ctypes.POINTER(PqLost), _V], ctypes.c_int),
+    "bcp_restore_plan": ([ctypes.c_uint64, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int,
+                          ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_int),
+                          ctypes.POINTER(ctypes.c_uint32)], ctypes.c_int),
     "bcp_pq_culprit": ([ctypes.POINTER(PqCheckResult), ctypes.POINTER(ctypes.c_int)], ctypes.c_int),
     "bcp_pq_repair_stripes_async": ([_V, ctypes.POINTER(Stripe), ctypes.c_uint32, ctypes.POINTER(Source),
                                      ctypes.c_uint32, ctypes.POINTER(ctypes.c_uint64),
@@ -407,6 +411,16 @@ def call(fn: str, *args) -> int:
 def q_target(locations: int, ntargets: int) -> int:
     """bcp_q_target: the storage target of an item's Q file, or -1."""
     return lib().bcp_q_target(locations, ntargets)
+
+
+def restore_plan(locations: int, ntargets: int, target_a: int, target_b: int = -1, q_on: bool = True,
+                 windowed_no_q: bool = False) -> tuple:
+    """bcp_restore_plan: (p_lost, q_lost, keep) for an item after target_a and target_b (-1: one) were lost;
+    keep is PQ_KEEP_Q, PQ_KEEP_P or 0 (nothing to keep)."""
+    pl, ql, keep = ctypes.c_int(0), ctypes.c_int(0), ctypes.c_uint32(0)
+    call("bcp_restore_plan", locations, ntargets, target_a, target_b, int(q_on), int(windowed_no_q),
+         ctypes.byref(pl), ctypes.byref(ql), ctypes.byref(keep))
+    return bool(pl.value), bool(ql.value), keep.value
 
 
 def pq_culprit(result) -> tuple:

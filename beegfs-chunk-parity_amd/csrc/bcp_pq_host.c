@@ -22,6 +22,23 @@ int bcp_q_target(uint64_t locations, int ntargets) {
     return -1;
 }
 
+/* Which of an item's parity files were lost with the targets, and which
+ * survivor is kept as the witness (bcp_task.h). */
+int bcp_restore_plan(uint64_t locations, int ntargets, int target_a, int target_b, int q_on, int windowed_no_q,
+                     int *p_lost, int *q_lost, uint32_t *keep) {
+    if (ntargets < 1 || ntargets > MAX_STORAGE_TARGETS) return -EINVAL;
+    if (target_a < 0 || target_a >= ntargets || target_b < -1 || target_b >= ntargets || target_b == target_a)
+        return -EINVAL;
+    const int p = GET_P(locations);
+    const int qt = q_on && !windowed_no_q ? bcp_q_target(locations, ntargets) : -1;
+    const int pl = p < ntargets && (p == target_a || p == target_b); /* NO_P (0xFF) is above every target */
+    const int ql = qt >= 0 && (qt == target_a || qt == target_b);
+    if (p_lost) *p_lost = pl;
+    if (q_lost) *q_lost = ql;
+    if (keep) *keep = pl && !ql && qt >= 0 ? BCP_PQ_KEEP_Q : ql && !pl ? BCP_PQ_KEEP_P : 0u;
+    return 0;
+}
+
 /* The single member a syndrome record blames, if it blames one. */
 int bcp_pq_culprit(const bcp_pq_check_result *r, int *position) {
     if (!r) return -EINVAL;

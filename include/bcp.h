@@ -61,7 +61,8 @@ extern "C" {
  * key "last_pq_repair_phases" and bcp_task.h's
  * bcp_pipeline_set_repair_windowed; the verified rebuild's
  * bcp_pq_rebuild_check_stripes_async / bcp_pq_rebuild_check_stripes_win_async,
- * and the "last_desc_form" values 12 and 13.
+ * and the "last_desc_form" values 12 and 13; the parity restore's rule,
+ * BCP_PQ_KEEP_P / BCP_PQ_KEEP_Q and bcp_task.h's bcp_restore_plan.
  * 3 (r05): the pipeline's MAP read mode (BCP_READ_MAP), its
  * bcp_pipeline_timing fields and bcp_host_register_dma_src removed.
  * 2 (r04): bcp_task.h's bcp_run_stats gained `refused`, bcp_pipeline_opts
@@ -252,6 +253,19 @@ int bcp_pq_recover_stripes_async(bcp_queue *q, const bcp_stripe *stripes, uint32
 int bcp_pq_rebuild_check_stripes_async(bcp_queue *q, const bcp_stripe *stripes, uint32_t nstripes,
                                        const bcp_source *sources, uint32_t nsources, const bcp_pq_lost *lost,
                                        bcp_check_result *results_dev);
+
+/* Parity restore: one of a complete item's two parity files is lost, the other
+ * survives and is the only witness of what the members held when both were
+ * written.  Which of the two is kept (bcp_task.h, bcp_restore_plan): */
+#define BCP_PQ_KEEP_P 1u /* P is the witness, Q is to be written */
+#define BCP_PQ_KEEP_Q 2u /* Q is the witness, P is to be written */
+/* With Ps = P ^ XOR_k D_k and Qs = Q ^ XOR_k g^k * D_k over the complete
+ * stripe, the kept parity agrees with the members at byte j when Ps[j] == 0
+ * (keep P) or Qs[j] == 0 (keep Q).  A fault confined to one member at offset j
+ * -- a data member (e in Ps, g^k * e in Qs) or the kept parity (e) -- always
+ * shows there, never zero.  Which member is wrong cannot be told from one
+ * syndrome.  Two members wrong at one offset can cancel (e in D_a and in D_b
+ * leaves Ps clean; e_a, e_b with g^a * e_a = g^b * e_b leave Qs clean). */
 
 /* One record per stripe of a syndrome check (bcp_pq_check_stripes_async).
  * With Ps = P ^ XOR_k D_k and Qs = Q ^ XOR_k g^k * D_k, a byte j is bad when

@@ -829,6 +829,22 @@ typedef struct { uint64_t xor_items, q_items, pq_items, unrecoverable; } bcp_reb
 int bcp_pipeline_rebuild2(bcp_pipeline *pl, const char *store_root, int ntargets, int target_a, int target_b,
                           const bcp_work_item *items, size_t nitems, const char *corrupt_list_path,
                           const char *lost_list_path, FILE *log, bcp_run_stats *stats, bcp_rebuild2_stats *st2);
+/* Parity restore, the rule (added under ABI 4; no device, no I/O): what became
+ * of an item's parity files when target_a and target_b (-1: one target) were
+ * lost, and which survivor can vouch for the other's restoration.  The item
+ * has a Q file by rule when q_on is set, bcp_q_target(locations, ntargets)
+ * names a target and the item is not windowed_no_q (max_cs > BCP_WINDOW_BYTES
+ * without bcp_pipeline_set_q_windowed).
+ *   *p_lost  the item has a P target (not NO_P) and it is a lost target
+ *   *q_lost  the item has a Q file by rule and its Q target is a lost target
+ *   *keep    BCP_PQ_KEEP_Q (bcp.h) when P is lost and the item's Q file is not,
+ *            BCP_PQ_KEEP_P when Q is lost and P is not, 0 when there is nothing
+ *            to keep: both lost, P lost with no Q by rule, or neither lost.
+ * Each pointer may be NULL.  -EINVAL for ntargets outside 1 ..
+ * MAX_STORAGE_TARGETS, target_a outside [0, ntargets), target_b outside
+ * [-1, ntargets) or equal to target_a. */
+int bcp_restore_plan(uint64_t locations, int ntargets, int target_a, int target_b, int q_on, int windowed_no_q,
+                     int *p_lost, int *q_lost, uint32_t *keep);
 /* bcp_gen_round with the batched pipeline as the engine; the replicas are
  * updated after the run, only when it finished without errors. */
 int bcp_gen_round_pipeline(bcp_pipeline *pl, const char *store_root, int ntargets, const bcp_eventset *events,
